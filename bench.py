@@ -19,7 +19,10 @@ N > 1 : configs[4] -- vertex-sharded csr_spmm (1-D row partition, halo rows exch
         worst_case_partition (random partition: (N-1)/N of the sources remote) and configs3_sage_replicas
         (tools/sage_bench.py --captured).
 
-One JSON line on stdout (rank 0).  Extra objects: roofline (dominant kernel, HIP-event timed inside the timed region;
+One JSON line on stdout (rank 0).  N = 1: a plain run sets up, warms up, times --steps steps and prints the headline (metric,
+value, unit, ms_per_step, dtype, config); --dump-outputs DIR also writes the last timed step's forward output and feature
+gradient (dump_outputs).  Everything below is measured with --full only, after the same timed steps.
+Extra objects: roofline (dominant kernel, HIP-event timed inside the timed region;
 `traffic` = PMC bytes measured by rocprofv3 passes inside this run; `rmat` and `hbm_resident` = the same kernel on the
 power-law topology and on a shard far beyond the caches) and cpu_baseline (the reference's own csr_spmm_cpu, built from
 /root/reference by oracle/Makefile, timed on this host's cores; N=1 only).  The N = 1 line also carries configs3_sage: the
@@ -54,6 +57,24 @@ def b_alg(nnz, m, f, s=4, s_w=4):
     """Algorithmic bytes of one csr_spmm launch: per edge colind + weight + one gathered row,
     per row rowptr + one output row."""
     return nnz * (4 + s_w + f * s) + m * (4 + f * s)
+
+
+DUMP_ROWS = 32768  # rows per dumped [nodes, F] output: 2 x 32768 x 128 x 4 B = 33.5 MB at the default width
+
+
+def dump_outputs(path, tensors):
+    """--dump-outputs: write what the last timed step returned to its caller as <path>/<name>.npy, float32.  Outputs with more
+    than DUMP_ROWS rows are cut to a fixed sample, the same for every run and every build: torch.randperm(rows, seed 0), the
+    first DUMP_ROWS, sorted."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in tensors.items():
+        t = t.detach().float()
+        if t.shape[0] > DUMP_ROWS:
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:DUMP_ROWS].sort().values
+            t = t.index_select(0, rows.to(t.device))
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(np.float32))
 
 
 def cpu_baseline(g, x, budget_s=10.0):
@@ -302,35 +323,36 @@ def bench_single(args):
     gd = g.to(dev)
     rowptr64, colind64 = gd.rowptr.long(), gd.colind.long()  # CogDL's Graph keeps int64 indices
     x = x_cpu.to(dev).requires_grad_()
-    gout = torch.randn(g.num_nodes, f, device=dev)
+
+    # the upstream gradient of every step, seeded: two runs with the same arguments see the same inputs (--dump-outputs)
+    gout = torch.randn(g.num_nodes, f, device=dev, generator=torch.Generator(device=dev).manual_seed(1))
 
     def step():
         # fresh int32 copies of the structure every call, as CogDL's dispatcher does (spmm_utils.py:106)
         out = csrspmm(rowptr64.int(), colind64.int(), x, gd.weight, True)
         x.grad = None
         out.backward(gout)
+        return out
 
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    # HIP events around the csr_spmm launches of every 4th step (both launches of it; at least 5 steps): a timing-event record
-    # costs the host ~18 us, four per step would make the timed loop host-bound on a slow box (spmm.KernelEventLog)
-    spmm_mod.KERNEL_EVENTS = spmm_mod.KernelEventLog(every=1)
+    # --full: HIP events around the csr_spmm launches of every 4th step (both launches of it; at least 5 steps): a timing-event
+    # record costs the host ~18 us, four per step would make the timed loop host-bound on a slow box (spmm.KernelEventLog)
+    log = spmm_mod.KernelEventLog(every=1) if args.full else None
+    spmm_mod.KERNEL_EVENTS = log
     sample_every = max(1, min(4, args.steps // 5))
     t0 = time.perf_counter()
     for i in range(args.steps):
-        spmm_mod.KERNEL_EVENTS.enabled = i % sample_every == 0  # (this step's two launches, or none)
-        step()
+        if log is not None:
+            log.enabled = i % sample_every == 0  # (this step's two launches, or none)
+        out = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    events, spmm_mod.KERNEL_EVENTS = list(spmm_mod.KERNEL_EVENTS), None
-    kern_ms = sum(a.elapsed_time(b) for a, b in events) / len(events)
+    spmm_mod.KERNEL_EVENTS = None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"spmm_out": out.detach(), "x_grad": x.grad})
 
-    fwd_ms = kernel_alone_ms(gd, x.detach())
-    traffic, traffic_info = pmc_traffic(args.topology, f, live=not args.no_pmc)
-
-    bytes_alg = b_alg(g.nnz, g.num_nodes, f)
-    achieved = bytes_alg / (kern_ms * 1e-3) / 1e9
     result = {
         "metric": "SpMM GEdges/s (csr_spmm fwd+bwd, ogbn-arxiv-shaped GCN aggregation) @1 GPU",
         "value": 2 * g.nnz * args.steps / dt / 1e9,
@@ -342,6 +364,17 @@ def bench_single(args):
         "config": {"workload": "ogbn-arxiv-like full-graph csr_spmm fwd+bwd (configs[1])", "nodes": g.num_nodes,
                    "nnz": g.nnz, "feat": f, "topology": args.topology, "weighted": True,
                    "parallelism": "single GPU"},
+    }
+    if not args.full:
+        return result
+
+    events = list(log)
+    kern_ms = sum(a.elapsed_time(b) for a, b in events) / len(events)
+    fwd_ms = kernel_alone_ms(gd, x.detach())
+    traffic, traffic_info = pmc_traffic(args.topology, f, live=not args.no_pmc)
+    bytes_alg = b_alg(g.nnz, g.num_nodes, f)
+    achieved = bytes_alg / (kern_ms * 1e-3) / 1e9
+    result.update({
         "roofline": {"bound": "hbm", "kernel": "rowreduce_main_kernel<SpmmOp<float,VEC=2,LPR=64,UNROLL=8,weighted,exact,no-epilogue>> (the HIP events bracket one "
                                "cogdl_hip_csr_spmm call = this kernel + the ~4 us rowreduce_combine_kernel)",
                      "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
@@ -354,7 +387,7 @@ def bench_single(args):
                                       "slow box)" % (sample_every, {1: "st", 2: "nd", 3: "rd"}.get(sample_every, "th"), 2 * args.steps),
                      "kernel_ms_fwd_alone": fwd_ms,
                      "GEdges_s_fwd_alone": g.nnz / (fwd_ms * 1e-3) / 1e9},
-    }
+    })
     result["roofline"]["rmat"] = rmat_roofline(dev)
     result["gnn_epoch"] = gcn_epoch_ms(gd, rowptr64, colind64, x)
     result["gnn_epoch"]["ms_with_torch_linear"] = gcn_epoch_ms(gd, rowptr64, colind64, x, mfma_linear=False)["ms"]
@@ -586,12 +619,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--feat", type=int, default=128)
     ap.add_argument("--topology", default="uniform", choices=["uniform", "rmat"])
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-gat", action="store_true", help="skip the configs2_gat leg (GAT on the Reddit-shaped graph, bf16)")
-    ap.add_argument("--no-trainer", action="store_true", help="skip the reference-Trainer epoch legs (gnn_epoch.trainer_ms)")
-    ap.add_argument("--no-shard-base", action="store_true", help="skip the weak_scaling_base leg (the sharded path at world size 1)")
-    ap.add_argument("--no-papers", action="store_true", help="skip the configs4_papers_1gpu leg (papers100M-shaped graph at full size on this GPU)")
-    ap.add_argument("--no-pmc", action="store_true", help="do not run the rocprofv3 --pmc passes for roofline.traffic")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: after the headline, also measure everything else the line carries (roofline, GCN epoch, CPU "
+                         "baseline, the configs[2]/[3]/[4] legs, ...); a plain run times the steps and prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N=1: write the last timed step's forward output and feature gradient to DIR/<name>.npy (float32; "
+                         "a fixed sample of %d rows)" % DUMP_ROWS)
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-gat", action="store_true", help="--full: skip the configs2_gat leg (GAT on the Reddit-shaped graph, bf16)")
+    ap.add_argument("--no-trainer", action="store_true", help="--full: skip the reference-Trainer epoch legs (gnn_epoch.trainer_ms)")
+    ap.add_argument("--no-shard-base", action="store_true", help="--full: skip the weak_scaling_base leg (the sharded path at world size 1)")
+    ap.add_argument("--no-papers", action="store_true", help="--full: skip the configs4_papers_1gpu leg (papers100M-shaped graph at full size on this GPU)")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: do not run the rocprofv3 --pmc passes for roofline.traffic")
     ap.add_argument("--sharded", action="store_true", help="run the N>1 workload (vertex-sharded SpMM) even at world size 1")
     ap.add_argument("--shard-nodes", type=int, default=0, help="N>1: nodes per GPU (default: papers100M/8)")
     ap.add_argument("--shard-degree", type=float, default=0.0, help="N>1: mean in-degree (default 28.8)")
@@ -620,6 +659,10 @@ def main():
     args.bench_script = os.path.abspath(__file__)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.gpus > 1 or args.sharded):
+        raise SystemExit("--dump-outputs is supported for the N = 1 line only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
     if not args.selftest_cpu and not torch.cuda.is_available():

@@ -1,6 +1,6 @@
-"""Drop-in check against the REAL reference package (build container only: skipped where /root/reference is absent,
-e.g. on the GPU box).  cogdl_amd.install() must make CogDL's own, unchanged code -- Graph, the spmm dispatcher,
-Graph.sample_adj, coo2csr_index, GCNLayer -- run on the cogdl_amd operators.  CPU-only here, so what is exercised is
+"""Drop-in check against the REAL reference package: the copy build() stages under oracle/_ref/pkg (oracle/Makefile `ref`),
+or $COGDL_REFERENCE; skipped where neither is present.  cogdl_amd.install() must make CogDL's own, unchanged code -- Graph,
+the spmm dispatcher, Graph.sample_adj, coo2csr_index, GCNLayer -- run on the cogdl_amd operators.  CPU-only here, so what is exercised is
 the host library (sampler, COO->CSR, CPU SpMM) plus the module plumbing; the GPU kernels behind the same names are
 covered by the -m gpu suite."""
 import os
@@ -10,7 +10,8 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.environ.get("COGDL_REFERENCE", "/root/reference")
+STAGED = os.path.join(ROOT, "oracle", "_ref", "pkg")
+REF = STAGED if os.path.isdir(os.path.join(STAGED, "cogdl")) else os.environ.get("COGDL_REFERENCE", "")
 
 SCRIPT = r'''
 import os, shutil, sys, tempfile
@@ -168,7 +169,7 @@ print("INSTALL-OK", served)
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "cogdl")), reason="reference package not present")
+@pytest.mark.skipif(not REF or not os.path.isdir(os.path.join(REF, "cogdl")), reason="reference package not present")
 def test_reference_package_runs_on_cogdl_amd_after_install():
     proc = subprocess.run([sys.executable, "-c", SCRIPT, ROOT, REF], capture_output=True, text=True, timeout=600)
     assert proc.returncode == 0 and "INSTALL-OK" in proc.stdout, proc.stdout[-2000:] + proc.stderr[-4000:]

@@ -18,14 +18,17 @@ if has variants; then
   timeout 900 python tools/spmm_variants.py > gpurun_out/variants.txt 2>&1; timeout 600 python tools/spmm_variants.py big >> gpurun_out/variants.txt 2>&1
   tail -5 gpurun_out/variants.txt
 fi
+# the bench and prof stages write under $BENCH_OUT (default: bench_out/ in the repository root)
+BENCH_OUT="${BENCH_OUT:-$(pwd)/bench_out}"; BENCH="$(pwd)/bench.py"
 if has bench; then
-  timeout 600 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err
-  cat gpurun_out/bench.json; tail -3 gpurun_out/bench.err
+  mkdir -p "$BENCH_OUT"
+  timeout 600 python bench.py --full > "$BENCH_OUT/bench.json" 2> "$BENCH_OUT/bench.err"
+  cat "$BENCH_OUT/bench.json"; tail -3 "$BENCH_OUT/bench.err"
 fi
 if has prof; then
-  rm -rf gpurun_out/prof_kt
-  (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -f csv -d "$GRAFT_REPO_ROOT/gpurun_out/prof_kt" -o kt -- python "$GRAFT_REPO_ROOT/bench.py" --no-cpu --no-shard-base) > gpurun_out/bench_prof.log 2>&1
-  find gpurun_out/prof_kt -name "*stats*" | head; 
+  rm -rf "$BENCH_OUT/prof_kt"; mkdir -p "$BENCH_OUT"
+  (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -f csv -d "$BENCH_OUT/prof_kt" -o kt -- python "$BENCH" --full --no-cpu --no-shard-base) > "$BENCH_OUT/bench_prof.log" 2>&1
+  find "$BENCH_OUT/prof_kt" -name "*stats*" | head
 fi
 if has ops; then
   timeout 1500 python tools/ops_bench.py --json gpurun_out/ops_bench.json > gpurun_out/ops_bench.txt 2>&1; echo "ops rc=$?" >> gpurun_out/ops_bench.txt
