@@ -111,6 +111,19 @@ HIP_SIGNATURES = {
     "cogdl_hip_csr2csc_i64_workspace_bytes": ([_vp, _i64], _sz),
     "cogdl_hip_csr2csc_i64": ([_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp], _i32),
     "cogdl_hip_gather_rows_i64": ([_vp, _vp, _vp, _i64, _i64, _i32, _vp], _i32),
+    # sparse x sparse product (csrc/spgemm.hip)
+    "cogdl_hip_spgemm_plan_bytes": ([_i64], _sz),
+    "cogdl_hip_spgemm_count_workspace_bytes": ([_i64], _sz),
+    "cogdl_hip_spgemm_count": ([_vp] * 4 + [_i64, _i64, _i64, _vp, _vp, _vp, _sz, _vp], _i32),
+    "cogdl_hip_spgemm_expand_workspace_bytes": ([_i64], _sz),
+    "cogdl_hip_spgemm_expand": ([_vp] * 6 + [_i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp], _i32),
+    "cogdl_hip_spgemm_rowptr_workspace_bytes": ([_i64], _sz),
+    "cogdl_hip_spgemm_rowptr": ([_vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp], _i32),
+    "cogdl_hip_spgemm_fill": ([_vp] * 6 + [_i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp], _i32),
+    "cogdl_hip_spgemm_grad_a": ([_vp] * 9 + [_i64, _i64, _vp], _i32),
+    "cogdl_hip_spgemm_grad_b": ([_vp] * 10 + [_i64, _i64, _vp], _i32),
+    "cogdl_hip_coo_dupsum_workspace_bytes": ([_i64], _sz),
+    "cogdl_hip_coo_dupsum": ([_vp] * 4 + [_i64, _i64] + [_vp] * 5 + [_sz, _vp], _i32),
 }
 
 MAX_SEGMENTS = 64  # COGDL_HIP_MAX_SEGMENTS

@@ -37,7 +37,7 @@ _finder = None
 
 
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
-            metis=False, big_graphs=False):
+            metis=False, big_graphs=False, torch_sparse=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -57,6 +57,9 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     graphs of 2^31 edges and more keep their int64 row pointer on the way to csrspmm (the reference's `.int()` wraps there).
     metis=True registers cogdl_amd.metis_compat as the module `metis` when the real package cannot be imported, so that
     ClusteredDataset / ClusteredLoader (cogdl/data/sampler.py:188-262) partition on the GPU instead of exiting.
+    torch_sparse=True registers cogdl_amd.torch_sparse_compat as the module `torch_sparse` when the real package cannot be
+    imported, so that the models that call torch_sparse.spspmm / spmm (srgcn, graph_unet, gtn) import and run: the sparse x
+    sparse product on the HIP SpGEMM (cogdl_amd.operators.spgemm), spmm on the COO message operator.
     linear=True additionally routes torch.nn.functional.linear -- i.e. the unchanged nn.Linear inside every CogDL
     layer -- through cogdl_amd.linear (hand-written MFMA weight gradient for full-graph shapes)."""
     global _finder
@@ -113,6 +116,11 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
             importlib.import_module("metis")  # the real one wins where it exists
         except Exception:  # (ImportError, or the wrapper's RuntimeError when libmetis is missing)
             sys.modules["metis"] = importlib.import_module("cogdl_amd.metis_compat")
+    if torch_sparse and "torch_sparse" not in sys.modules:
+        try:
+            importlib.import_module("torch_sparse")  # the real one wins where it exists
+        except Exception:
+            sys.modules["torch_sparse"] = importlib.import_module("cogdl_amd.torch_sparse_compat")
     su = sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):
@@ -169,6 +177,8 @@ def _rebind_graph_build():
 
 
 def uninstall():
+    if getattr(sys.modules.get("torch_sparse"), "__name__", "") == "cogdl_amd.torch_sparse_compat":
+        del sys.modules["torch_sparse"]
     if "cogdl_amd.big_dispatch" in sys.modules:
         sys.modules["cogdl_amd.big_dispatch"].uninstall()
     if "cogdl_amd.structure_memo" in sys.modules:

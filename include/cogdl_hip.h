@@ -675,6 +675,68 @@ COGDL_API int cogdl_hip_shard_fill(const int64_t *rowptr, const int64_t *col, co
 COGDL_API int cogdl_hip_bfs_step(const int64_t *rowptr, const int64_t *col, int64_t n, int32_t *level, int32_t cur,
                        int *changed, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * spgemm: C = A . B, A [m, k] and B [k, n] int32 CSR with fp32 values, C canonical CSR (columns ascending and unique
+ * inside a row).  The contract of torch_sparse.spspmm (reached by the reference's srgcn / graph_unet / gtn models)
+ * and of torch.sparse.mm: the pattern is STRUCTURAL -- every (i, j) with a product A[i,k] B[k,j] is in C, an entry
+ * whose products sum to 0.0 included.  A and B need not be canonical (duplicate columns are summed like any other
+ * products).  Every value of C is the sum of its products in expansion order (A_i's entries in CSR order, then B_k's),
+ * added by one thread: bit-identical results on every call, no float atomics.  m, k, n < 2^31, nnz(C) < 2^31.
+ * The output size depends on the data, so a product is a short host-driven sequence (not hipGraph-capturable):
+ *   1. count   plan: caller-owned, cogdl_hip_spgemm_plan_bytes(m) bytes (8-byte aligned), kept until fill.
+ *              Writes rowptrC [m+1] and the plan's DEVICE header, int64 hdr[8] at the plan's start:
+ *              hdr[3] = n_hub (rows whose products exceed the 4096 an LDS table holds), hdr[4] = their number of
+ *              products, hdr[5] = nnz(C) (hub rows counted as 0 while n_hub > 0).  The caller reads the header: the
+ *              one synchronisation of a product without hub rows; rowptrC is valid only when hdr[5] < 2^31.
+ *   2. hub rows only (hdr[3] > 0): expand writes their products, row by row in expansion order, as a CSR
+ *              hub_rowptr [n_hub+1], hub_col / hub_val [hdr[4]] (hdr[4] <= COGDL_HIP_SEGMENT_MAX_EDGES, else
+ *              COGDL_HIP_ERANGE); the caller makes it canonical (cogdl_hip_csr2csc twice, then cogdl_hip_coo_dupsum with
+ *              the composed permutation: sums in expansion order) and passes the canonical CSR to rowptr, which
+ *              rewrites rowptrC and hdr[5] (a second synchronisation), and to fill.
+ *   3. fill    colC / valC [nnzC] (nnzC = hdr[5] as read by the caller).
+ * count / rowptr workspace: cogdl_hip_spgemm_count_workspace_bytes(m); expand: cogdl_hip_spgemm_expand_workspace_bytes.
+ * Backward (values only; every output has one owner, no atomics):
+ *   grad_a: gradA[(i,k)] = sum_j gradC[i,j] B[k,j]  (B_k's entries looked up in row i of C; needs C canonical)
+ *   grad_b: gradB[(k,j)] = sum_i A[i,k] gradC[i,j]  over column k of A: colptrAT [k+1] / rowindAT / permAT of
+ *           cogdl_hip_csr2csc(rowptrA, colA, m, k), A's values read as valA[permAT[q]].
+ * ------------------------------------------------------------------------------------- */
+COGDL_API size_t cogdl_hip_spgemm_plan_bytes(int64_t m);
+COGDL_API size_t cogdl_hip_spgemm_count_workspace_bytes(int64_t m);
+COGDL_API int cogdl_hip_spgemm_count(const int32_t *rowptrA, const int32_t *colA, const int32_t *rowptrB, const int32_t *colB,
+                           int64_t m, int64_t k, int64_t n, void *plan, int32_t *rowptrC, void *workspace,
+                           size_t workspace_bytes, void *stream);
+COGDL_API size_t cogdl_hip_spgemm_expand_workspace_bytes(int64_t n_hub);
+COGDL_API int cogdl_hip_spgemm_expand(const int32_t *rowptrA, const int32_t *colA, const float *valA, const int32_t *rowptrB,
+                            const int32_t *colB, const float *valB, int64_t m, const void *plan, int64_t n_hub,
+                            int64_t hub_products, int32_t *hub_rowptr, int32_t *hub_col, float *hub_val, void *workspace,
+                            size_t workspace_bytes, void *stream);
+COGDL_API size_t cogdl_hip_spgemm_rowptr_workspace_bytes(int64_t m);
+COGDL_API int cogdl_hip_spgemm_rowptr(void *plan, int64_t m, int64_t n_hub, const int32_t *hub_rowptr, int32_t *rowptrC,
+                            void *workspace, size_t workspace_bytes, void *stream);
+COGDL_API int cogdl_hip_spgemm_fill(const int32_t *rowptrA, const int32_t *colA, const float *valA, const int32_t *rowptrB,
+                          const int32_t *colB, const float *valB, int64_t m, int64_t k, int64_t n, const void *plan,
+                          const int32_t *rowptrC, int64_t nnzC, int32_t *colC, float *valC, int64_t n_hub,
+                          const int32_t *hub_rowptr, const int32_t *hub_col, const float *hub_val, void *stream);
+COGDL_API int cogdl_hip_spgemm_grad_a(const int32_t *rowptrA, const int32_t *colA, const int32_t *rowptrB, const int32_t *colB,
+                            const float *valB, const int32_t *rowptrC, const int32_t *colC, const float *gradC,
+                            float *gradA, int64_t m, int64_t nnzA, void *stream);
+COGDL_API int cogdl_hip_spgemm_grad_b(const int32_t *colptrAT, const int32_t *rowindAT, const int32_t *permAT, const float *valA,
+                            const int32_t *rowptrB, const int32_t *colB, const int32_t *rowptrC, const int32_t *colC,
+                            const float *gradC, float *gradB, int64_t k, int64_t nnzB, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * coo_dupsum: the segmented duplicate sum of COO canonicalisation.  In: a CSR whose rows are sorted by column
+ * (duplicates adjacent) -- rowptr [rows+1], col [nnz] -- and `order` [nnz] (NULL = identity): sorted position t holds
+ * input entry order[t].  Out: rowptr_u [rows+1] and col_u of the distinct (row, col) pairs, val_u[u] = the sum of
+ * val[order[t]] over the run, added in sorted order by one thread (val / val_u may both be NULL: structure only),
+ * map[order[t]] = u (NULL: not written).  col_u / val_u need room for rowptr_u[rows] <= nnz entries.
+ * workspace: cogdl_hip_coo_dupsum_workspace_bytes(nnz), 256-byte aligned.  nnz <= COGDL_HIP_SEGMENT_MAX_EDGES.
+ * ------------------------------------------------------------------------------------- */
+COGDL_API size_t cogdl_hip_coo_dupsum_workspace_bytes(int64_t nnz);
+COGDL_API int cogdl_hip_coo_dupsum(const int32_t *rowptr, const int32_t *col, const int32_t *order, const float *val,
+                         int64_t rows, int64_t nnz, int32_t *rowptr_u, int32_t *col_u, float *val_u, int32_t *map,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
