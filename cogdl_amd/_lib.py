@@ -16,6 +16,7 @@ HOST_LIB_PATH = os.path.join(_CSRC, "libcogdl_host.so")
 
 _vp, _i64, _i32, _f32, _sz, _u64 = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float,
                                      ctypes.c_size_t, ctypes.c_uint64)
+_f64 = ctypes.c_double
 
 # name -> (argtypes, restype): must list every symbol declared in include/cogdl_hip.h
 HIP_SIGNATURES = {
@@ -124,6 +125,9 @@ HIP_SIGNATURES = {
     "cogdl_hip_spgemm_grad_b": ([_vp] * 10 + [_i64, _i64, _vp], _i32),
     "cogdl_hip_coo_dupsum_workspace_bytes": ([_i64], _sz),
     "cogdl_hip_coo_dupsum": ([_vp] * 4 + [_i64, _i64] + [_vp] * 5 + [_sz, _vp], _i32),
+    # random walks (csrc/walk.hip)
+    "cogdl_hip_random_walk": ([_vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _u64, _vp, _vp, _vp], _i32),
+    "cogdl_hip_node2vec_walk": ([_vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _f64, _i32, _u64, _vp, _vp, _vp, _vp], _i32),
 }
 
 MAX_SEGMENTS = 64  # COGDL_HIP_MAX_SEGMENTS
@@ -143,6 +147,8 @@ HOST_SIGNATURES = {
     "cogdl_host_subgraph": ([_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp], _i32),
     "cogdl_host_csr_spmm_f32": ([_vp] * 5 + [_i64, _i64, _i32], _i32),
     "cogdl_host_csr_spmm_f32_i64": ([_vp] * 5 + [_i64, _i64, _i32], _i32),
+    "cogdl_host_random_walk": ([_vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _u64, _vp, _vp], _i32),
+    "cogdl_host_node2vec_walk": ([_vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _f64, _i32, _u64, _vp, _vp, _vp], _i32),
 }
 
 EUNSUPPORTED = 7  # COGDL_HIP_EUNSUPPORTED

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/cogdl_host.h"
+#include "walk_draw.h"
 
 namespace {
 
@@ -409,6 +410,78 @@ int cogdl_host_csr_spmm_f32(const int32_t *rowptr, const int32_t *colind, const 
 int cogdl_host_csr_spmm_f32_i64(const int64_t *rowptr, const int32_t *colind, const float *val, const float *dense,
                                 float *out, int64_t m, int64_t k, int nthreads) {
     return spmm_threads(rowptr, colind, val, dense, out, m, k, nthreads, spmm_rows64);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- random walks (the twin of csrc/walk.hip)
+// The draws and the rules of a step are walk_draw.h's, the same functions the kernels run: equal arrays for equal inputs.
+namespace {
+namespace wk = cogdl_walk;
+
+int walk_args_status(const int64_t *indptr, const int64_t *indices, int64_t num_nodes, int64_t num_edges,
+                     const int64_t *start, int64_t n_walkers, int64_t length, const int64_t *walks, const int *flags) {
+    if (num_nodes < 0 || num_edges < 0 || n_walkers < 0 || length < 1 || length > 0x7fffffff || !flags) return COGDL_HOST_EINVAL;
+    if (n_walkers > 0 && (!indptr || !start || !walks)) return COGDL_HOST_EINVAL;
+    if (num_edges > 0 && !indices) return COGDL_HOST_EINVAL;
+    return COGDL_HOST_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int cogdl_host_random_walk(const int64_t *indptr, const int64_t *indices, int64_t num_nodes, int64_t num_edges,
+                           const int64_t *start, int64_t n_walkers, int64_t length, double restart_p, uint64_t seed,
+                           int64_t *walks, int *flags) {
+    const int rc = walk_args_status(indptr, indices, num_nodes, num_edges, start, n_walkers, length, walks, flags);
+    if (rc != COGDL_HOST_OK) return rc;
+    if (!(restart_p >= 0.0 && restart_p <= 1.0)) return COGDL_HOST_EINVAL;
+    const wk::Graph g = {indptr, indices, num_nodes, num_edges};
+    const uint64_t restart_t = wk::fixed32(restart_p);
+    int all = 0;
+#pragma omp parallel for schedule(static) reduction(| : all) if (n_walkers * length >= 4096)
+    for (int64_t w = 0; w < n_walkers; ++w) {
+        int64_t *out = walks + w * length;
+        const int64_t first = start[w];
+        int64_t cur = first;
+        int err = wk::valid_id(g, cur) ? 0 : wk::kBadStart;
+        out[0] = cur;
+        for (int64_t i = 1; i < length; ++i) out[i] = cur = wk::step_first_order(g, seed, w, i, first, cur, restart_t, err);
+        all |= err;
+    }
+    *flags = all;
+    return COGDL_HOST_OK;
+}
+
+int cogdl_host_node2vec_walk(const int64_t *indptr, const int64_t *indices, int64_t num_nodes, int64_t num_edges,
+                             const int64_t *start, int64_t n_walkers, int64_t length, double p, double q, int max_trials,
+                             uint64_t seed, int64_t *walks, int32_t *fallback_steps, int *flags) {
+    const int rc = walk_args_status(indptr, indices, num_nodes, num_edges, start, n_walkers, length, walks, flags);
+    if (rc != COGDL_HOST_OK) return rc;
+    if (!(p > 0.0) || !(q > 0.0) || !(p < 1e300) || !(q < 1e300) || max_trials < 0 || max_trials > (1 << 20)) return COGDL_HOST_EINVAL;
+    if (max_trials == 0) max_trials = wk::kDefaultTrials;
+    const wk::Graph g = {indptr, indices, num_nodes, num_edges};
+    const wk::N2vWeights wt = wk::n2v_weights(p, q);
+    int all = 0;
+#pragma omp parallel for schedule(dynamic, 64) reduction(| : all) if (n_walkers * length >= 4096)
+    for (int64_t w = 0; w < n_walkers; ++w) {
+        int64_t *out = walks + w * length;
+        int64_t prev = start[w], cur = prev;
+        int err = wk::valid_id(g, cur) ? 0 : wk::kBadStart;
+        int32_t n_fallback = 0;
+        out[0] = cur;
+        for (int64_t i = 1; i < length; ++i) {
+            bool fell_back;
+            const int64_t nxt = wk::step_node2vec(g, seed, w, i, prev, cur, wt, max_trials, err, fell_back);
+            n_fallback += fell_back ? 1 : 0;
+            prev = cur;
+            out[i] = cur = nxt;
+        }
+        if (fallback_steps) fallback_steps[w] = n_fallback;
+        all |= err;
+    }
+    *flags = all;
+    return COGDL_HOST_OK;
 }
 
 }  // extern "C"

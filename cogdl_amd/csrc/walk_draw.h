@@ -1,0 +1,210 @@
+// walk_draw.h -- the random draws and the per-step rules of the random walks, shared by the HIP kernels (walk.hip)
+// and their host twin (host_ops.cpp).  Plain C++: no HIP runtime, no libc beyond <stdint.h>; libcogdl_host.so includes
+// it and must stay HIP-free.  Because both sides run the SAME functions on the same integers, a walk is the same array
+// on the GPU and on the host, bit for bit.
+//
+// Randomness.  Every draw is a pure function of (seed, walker w, step i, trial) through Philox4x32-10 (Salmon et al.,
+// SC'11; the round function is restated here because philox.h pulls in the HIP runtime):
+//     (x, y, z, w) = philox4x32_10(counter = (w_lo, w_hi, i, trial), key = (seed_lo, seed_hi))
+//     restart?         x < T,  T = round(restart_p * 2^32) as a 64-bit number, so restart_p = 0 never restarts and
+//                      restart_p = 1 (T = 2^32) always does
+//     which neighbour  mulhi64((y << 32) | z, deg): uniform over [0, deg) with a bias below deg / 2^64, and able to
+//                      return deg - 1
+//     accept?          w < A,  A = round(weight / max weight * 2^32) (node2vec rejection sampling; A = 2^32 accepts always)
+// The first-order walk uses trial 0 only.  node2vec uses trials 0 .. max_trials - 1 for its rejection loop and trial
+// `max_trials` for the one draw of the exact fallback: r = mulhi64((y << 32) | z, total weight).
+// Nothing depends on launch shape, thread count or the order in which walkers are processed.
+//
+// Weights of node2vec are 32.32 fixed-point integers (the A above): rejection loop and fallback sample exactly the same
+// law, proportional to A_back : A_near : A_far, which differs from 1/p : 1 : 1/q by a relative 2^-32 at most.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIP__) || defined(__HIPCC__)
+#define COGDL_WALK_FN __attribute__((host)) __attribute__((device)) inline __attribute__((always_inline))
+#else
+#define COGDL_WALK_FN inline
+#endif
+#if defined(__clang__)
+#define COGDL_WALK_UNROLL _Pragma("unroll")
+#else
+#define COGDL_WALK_UNROLL
+#endif
+
+namespace cogdl_walk {
+
+enum : int {
+    kBadStart = 1,      // a start id outside [0, N)
+    kBadNeighbour = 2,  // a neighbour id outside [0, N)
+    kBadRowPtr = 4      // a row of indptr that is not inside [0, E] or runs backwards
+};
+
+constexpr int kDefaultTrials = 256;  // node2vec: rejection trials per step before the exact pass over the row
+
+struct Draw {
+    uint32_t x, y, z, w;
+};
+
+COGDL_WALK_FN Draw philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+    const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+    COGDL_WALK_UNROLL
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)M0 * c0, p1 = (uint64_t)M1 * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += W0;
+        k1 += W1;
+    }
+    return {c0, c1, c2, c3};
+}
+
+COGDL_WALK_FN Draw draw(uint64_t seed, int64_t walker, int64_t step, uint32_t trial) {
+    return philox4x32_10((uint32_t)(uint64_t)walker, (uint32_t)((uint64_t)walker >> 32), (uint32_t)step, trial,
+                         (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+
+// High 64 bits of a 64 x 64 -> 128-bit product, from 32-bit halves (the same code on both compilers).
+COGDL_WALK_FN uint64_t mulhi64(uint64_t a, uint64_t b) {
+    const uint64_t al = a & 0xffffffffu, ah = a >> 32, bl = b & 0xffffffffu, bh = b >> 32;
+    const uint64_t p0 = al * bl, p1 = al * bh, p2 = ah * bl, p3 = ah * bh;
+    const uint64_t mid = (p0 >> 32) + (p1 & 0xffffffffu) + (p2 & 0xffffffffu);
+    return p3 + (p1 >> 32) + (p2 >> 32) + (mid >> 32);
+}
+
+COGDL_WALK_FN bool draw_restart(const Draw &d, uint64_t restart_t) { return (uint64_t)d.x < restart_t; }
+COGDL_WALK_FN int64_t draw_below(const Draw &d, uint64_t n) { return (int64_t)mulhi64(((uint64_t)d.y << 32) | d.z, n); }
+COGDL_WALK_FN bool draw_accept(const Draw &d, uint64_t a) { return (uint64_t)d.w < a; }
+
+// round(v * 2^32) for v in [0, 1], host side (called once per call by both libraries, in double)
+inline uint64_t fixed32(double v) {
+    if (!(v > 0.0)) return 0;
+    if (v >= 1.0) return (uint64_t)1 << 32;
+    return (uint64_t)(v * 4294967296.0 + 0.5);
+}
+
+struct N2vWeights {
+    uint64_t back, near, far;  // x == t, t in row x, neither; the largest is 2^32
+};
+inline N2vWeights n2v_weights(double p, double q) {
+    const double wb = 1.0 / p, wf = 1.0 / q;
+    double m = 1.0;
+    if (wb > m) m = wb;
+    if (wf > m) m = wf;
+    N2vWeights w = {fixed32(wb / m), fixed32(1.0 / m), fixed32(wf / m)};
+    if (w.back == 0) w.back = 1;  // (a weight below 2^-32 of the largest still has to be reachable in the fallback)
+    if (w.near == 0) w.near = 1;
+    if (w.far == 0) w.far = 1;
+    return w;
+}
+
+struct Graph {
+    const int64_t *indptr, *indices;
+    int64_t n, e;
+};
+
+// Row `v` (a valid id) -> [beg, beg + deg); false and kBadRowPtr if indptr does not describe a range inside indices.
+COGDL_WALK_FN bool row_of(const Graph &g, int64_t v, int64_t &beg, int64_t &deg, int &err) {
+    beg = g.indptr[v];
+    const int64_t end = g.indptr[v + 1];
+    deg = end - beg;
+    if (beg < 0 || end > g.e || deg < 0) {
+        err |= kBadRowPtr;
+        return false;
+    }
+    return true;
+}
+
+COGDL_WALK_FN bool valid_id(const Graph &g, int64_t v) { return (uint64_t)v < (uint64_t)g.n; }
+
+// One step of the first-order walk with restart.  `cur` is returned unchanged (the walker stays) at a node without
+// out-neighbours and after any error: a walker that has raised a flag reads nothing more.
+COGDL_WALK_FN int64_t step_first_order(const Graph &g, uint64_t seed, int64_t walker, int64_t step, int64_t start,
+                                       int64_t cur, uint64_t restart_t, int &err) {
+    if (err) return cur;
+    const Draw d = draw(seed, walker, step, 0u);
+    const int64_t src = draw_restart(d, restart_t) ? start : cur;
+    int64_t beg, deg;
+    if (!row_of(g, src, beg, deg, err) || deg == 0) return cur;
+    const int64_t x = g.indices[beg + draw_below(d, (uint64_t)deg)];
+    if (!valid_id(g, x)) {
+        err |= kBadNeighbour;
+        return cur;
+    }
+    return x;
+}
+
+// Is `t` in row `x` (sorted by column)?  Binary search, 64-bit offsets.
+COGDL_WALK_FN bool has_edge(const Graph &g, int64_t x, int64_t t, int &err) {
+    int64_t lo, deg;
+    if (!row_of(g, x, lo, deg, err)) return false;
+    const int64_t end = lo + deg;
+    int64_t hi = end;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (g.indices[mid] < t) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < end && g.indices[lo] == t;
+}
+
+// node2vec weight of moving to x with previous node t (x already validated)
+COGDL_WALK_FN uint64_t n2v_weight(const Graph &g, const N2vWeights &wt, int64_t x, int64_t t, int &err) {
+    if (x == t) return wt.back;
+    if (wt.near == wt.far) return wt.near;  // q = 1: the membership test cannot change the weight
+    return has_edge(g, x, t, err) ? wt.near : wt.far;
+}
+
+// One step of the node2vec walk: previous node t, current node v.  step 1 (no previous node yet) is uniform.
+// `fell_back` is set when the exact pass over the row decided the step.
+COGDL_WALK_FN int64_t step_node2vec(const Graph &g, uint64_t seed, int64_t walker, int64_t step, int64_t t, int64_t v,
+                                    const N2vWeights &wt, int max_trials, int &err, bool &fell_back) {
+    fell_back = false;
+    if (err) return v;
+    int64_t beg, deg;
+    if (!row_of(g, v, beg, deg, err) || deg == 0) return v;
+    if (step == 1) {
+        const int64_t x = g.indices[beg + draw_below(draw(seed, walker, step, 0u), (uint64_t)deg)];
+        if (!valid_id(g, x)) {
+            err |= kBadNeighbour;
+            return v;
+        }
+        return x;
+    }
+    for (int trial = 0; trial < max_trials; ++trial) {
+        const Draw d = draw(seed, walker, step, (uint32_t)trial);
+        const int64_t x = g.indices[beg + draw_below(d, (uint64_t)deg)];
+        if (!valid_id(g, x)) {
+            err |= kBadNeighbour;
+            return v;
+        }
+        const uint64_t a = n2v_weight(g, wt, x, t, err);
+        if (err) return v;
+        if (draw_accept(d, a)) return x;
+    }
+    // exact: total weight of the row, then the inverse CDF at r in [0, total)
+    fell_back = true;
+    uint64_t total = 0;
+    for (int64_t e = beg; e < beg + deg; ++e) {
+        const int64_t x = g.indices[e];
+        if (!valid_id(g, x)) {
+            err |= kBadNeighbour;
+            return v;
+        }
+        total += n2v_weight(g, wt, x, t, err);
+        if (err) return v;
+    }
+    const uint64_t r = (uint64_t)draw_below(draw(seed, walker, step, (uint32_t)max_trials), total);
+    uint64_t acc = 0;
+    for (int64_t e = beg; e < beg + deg; ++e) {
+        const int64_t x = g.indices[e];
+        acc += n2v_weight(g, wt, x, t, err);
+        if (r < acc) return x;
+    }
+    return v;  // unreachable: r < total = the final acc
+}
+
+}  // namespace cogdl_walk

@@ -37,7 +37,7 @@ _finder = None
 
 
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
-            metis=False, big_graphs=False, torch_sparse=False):
+            metis=False, big_graphs=False, torch_sparse=False, random_walk=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -60,6 +60,11 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     torch_sparse=True registers cogdl_amd.torch_sparse_compat as the module `torch_sparse` when the real package cannot be
     imported, so that the models that call torch_sparse.spspmm / spmm (srgcn, graph_unet, gtn) import and run: the sparse x
     sparse product on the HIP SpGEMM (cogdl_amd.operators.spgemm), spmm on the COO message operator.
+    random_walk=True rebinds the name `RandomWalker` in cogdl.utils.sampling, cogdl.utils, cogdl.data.data and
+    cogdl.data.sampler (opt-in: the walks then come from a different generator than the reference's) to
+    cogdl_amd.random_walk_compat.RandomWalker: Graph.random_walk / random_walk_with_restart and the unsupervised sampler's
+    positive pairs run on the library's walk operators (HIP kernels for a graph on the GPU, the OpenMP host twin otherwise)
+    instead of the reference's numba / interpreted Python loop.
     linear=True additionally routes torch.nn.functional.linear -- i.e. the unchanged nn.Linear inside every CogDL
     layer -- through cogdl_amd.linear (hand-written MFMA weight gradient for full-graph shapes)."""
     global _finder
@@ -121,6 +126,8 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
             importlib.import_module("torch_sparse")  # the real one wins where it exists
         except Exception:
             sys.modules["torch_sparse"] = importlib.import_module("cogdl_amd.torch_sparse_compat")
+    if random_walk:
+        _rebind_random_walker()
     su = sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):
@@ -176,7 +183,30 @@ def _rebind_graph_build():
             setattr(mod, fn, getattr(graph_build, fn))
 
 
+_RANDOM_WALKER_MODULES = ("cogdl.utils.sampling", "cogdl.utils", "cogdl.data.data", "cogdl.data.sampler")
+
+
+def _rebind_random_walker():
+    """The four modules that hold the reference's RandomWalker by name (`from cogdl.utils import RandomWalker` copies it) are
+    imported if need be and rebound; the originals are kept for uninstall()."""
+    from .random_walk_compat import RandomWalker
+
+    for name in _RANDOM_WALKER_MODULES:
+        _import_target(name, "random_walk")
+        mod = sys.modules[name]
+        cur = getattr(mod, "RandomWalker", None)
+        if cur is None:
+            raise _lib_error("install(random_walk=True): %s has no RandomWalker to rebind" % name)
+        if cur is not RandomWalker:
+            mod.__dict__.setdefault("_cogdl_amd_orig_random_walker", cur)
+            mod.RandomWalker = RandomWalker
+
+
 def uninstall():
+    for name in _RANDOM_WALKER_MODULES:
+        mod = sys.modules.get(name)
+        if mod is not None and "_cogdl_amd_orig_random_walker" in mod.__dict__:
+            mod.RandomWalker = mod.__dict__.pop("_cogdl_amd_orig_random_walker")
     if getattr(sys.modules.get("torch_sparse"), "__name__", "") == "cogdl_amd.torch_sparse_compat":
         del sys.modules["torch_sparse"]
     if "cogdl_amd.big_dispatch" in sys.modules:

@@ -7,8 +7,18 @@
     fused_gat.py     fused_gat_func                         (cogdl/operators/fused_gat.py)
     sample.py        sample_adj_c, subgraph_c, coo2csr_cpu, coo2csr_cpu_index  (cogdl/operators/sample.py)
 
+    walk.py          random_walk, node2vec_walk (also exported here)   (cogdl/utils/sampling.py, models/emb/node2vec.py)
+
     ops.py           scatter_add, op_aggr, s_*_e_sum / s_*_e_mean (fused HIP), s_*_e, s_*_t   (cogdl/operators/ops.py)
 
 Submodules are imported lazily: GPU modules load libcogdl_hip.so at import and raise if it
 is missing; `sample` only needs libcogdl_host.so and is safe in forked CPU workers.
 """
+
+
+def __getattr__(name):
+    if name in ("random_walk", "node2vec_walk"):
+        from . import walk
+
+        return getattr(walk, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -737,6 +737,41 @@ COGDL_API int cogdl_hip_coo_dupsum(const int32_t *rowptr, const int32_t *col, co
                          int64_t rows, int64_t nnz, int32_t *rowptr_u, int32_t *col_u, float *val_u, int32_t *map,
                          void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Random walks on a GPU-resident CSR graph (csrc/walk.hip): int64 indptr[num_nodes + 1] / indices[num_edges] (what
+ * cogdl.data.Graph holds and cogdl_hip_sample_adj takes), int64 start[W], result int64 walks[W, length] row-major.
+ * Stream-ordered, one launch (plus one word fill), no host round trip, no atomics, no workspace; hipGraph-capturable.
+ * Replaces the numba / interpreted loops of cogdl/utils/sampling.py:14-67 (RandomWalker.walk) and the transition rule
+ * of cogdl/models/emb/node2vec.py:143-156.  Host twin with identical results: cogdl_host_random_walk /
+ * cogdl_host_node2vec_walk (include/cogdl_host.h).
+ *   random_walk    walks[w, 0] = start[w].  Step i >= 1: with probability 1 - restart_p the walker moves to a uniformly
+ *                  drawn out-neighbour of its current node, with probability restart_p to a uniformly drawn
+ *                  out-neighbour of its START node (as in the reference, a restart lands on a neighbour of the start, not
+ *                  on the start).  restart_p in [0, 1]: 0 never restarts, 1 always does.
+ *   node2vec_walk  unweighted graph, return parameter p > 0, in-out parameter q > 0.  Step 1 is uniform; afterwards, with
+ *                  previous node t and current node v, a neighbour x of v has weight 1/p if x == t, 1 if t is in row x
+ *                  of the CSR, else 1/q.  ROWS MUST BE SORTED BY COLUMN (the membership test is a binary search).
+ *                  Rejection sampling against max(1, 1/p, 1/q) for at most max_trials trials per step (0 = the default,
+ *                  256), then one exact pass over the row (weights summed, inverse CDF): the law is exact and every step
+ *                  terminates.  Weights are 32.32 fixed point relative to the largest.  Rows of fewer than 2^32 edges.
+ *                  fallback_steps: NULL, or device int32[W] receiving per walker the number of steps the exact pass decided.
+ *   Dead ends      A node without out-neighbours: the reference is undefined there (random.randint on an empty range).
+ *                  Here the walker stays and the node is repeated, so every entry of walks is a valid node id.
+ *   Randomness     a pure function of (seed, walker w, step i, trial) through Philox4x32-10 (csrc/walk_draw.h), independent
+ *                  of launch shape and scheduling; length < 2^31.
+ *   flags          DEVICE int, zeroed by the call: bit 0 a start id outside [0, num_nodes), bit 1 a neighbour id outside,
+ *                  bit 2 a row of indptr that is not a range inside [0, num_edges].  A walker that meets one parks (repeats
+ *                  its node, reads nothing more); nothing is read out of bounds.  Non-zero marks an invalid result; when
+ *                  several conditions occur in one call a bit may be missing, the word is never zero then.
+ *   W = 0 and length = 1 are valid; offsets are 64-bit throughout (num_edges >= 2^31 is fine).
+ * ------------------------------------------------------------------------------------- */
+COGDL_API int cogdl_hip_random_walk(const int64_t *indptr, const int64_t *indices, int64_t num_nodes, int64_t num_edges,
+                          const int64_t *start, int64_t n_walkers, int64_t length, double restart_p, uint64_t seed,
+                          int64_t *walks, int *flags, void *stream);
+COGDL_API int cogdl_hip_node2vec_walk(const int64_t *indptr, const int64_t *indices, int64_t num_nodes, int64_t num_edges,
+                            const int64_t *start, int64_t n_walkers, int64_t length, double p, double q, int max_trials,
+                            uint64_t seed, int64_t *walks, int32_t *fallback_steps, int *flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,21 @@ COGDL_HOST_API int cogdl_host_csr_spmm_f32(const int32_t *rowptr, const int32_t 
 COGDL_HOST_API int cogdl_host_csr_spmm_f32_i64(const int64_t *rowptr, const int32_t *colind, const float *val,
                                                const float *dense, float *out, int64_t m, int64_t k, int nthreads);
 
+/* Random walks on a CSR graph (int64 indptr[num_nodes + 1], indices[num_edges]), one walker per entry of start[W],
+ * written to walks[W, length] row-major; the host twin of cogdl_hip_random_walk / cogdl_hip_node2vec_walk
+ * (include/cogdl_hip.h, where the contract is spelled out): same arguments minus the stream, and for equal inputs and
+ * seed EXACTLY the array the GPU returns -- both read their draws from csrc/walk_draw.h.  OpenMP over the walkers; the
+ * result does not depend on the number of threads.  *flags (host int): bit 0 a start id outside [0, num_nodes), bit 1 a
+ * neighbour id outside, bit 2 a malformed row of indptr; non-zero marks an invalid result (nothing is read out of bounds).
+ * fallback_steps: NULL, or int32[W] receiving per walker the number of steps decided by the exact pass. */
+COGDL_HOST_API int cogdl_host_random_walk(const int64_t *indptr, const int64_t *indices, int64_t num_nodes,
+                                          int64_t num_edges, const int64_t *start, int64_t n_walkers, int64_t length,
+                                          double restart_p, uint64_t seed, int64_t *walks, int *flags);
+COGDL_HOST_API int cogdl_host_node2vec_walk(const int64_t *indptr, const int64_t *indices, int64_t num_nodes,
+                                            int64_t num_edges, const int64_t *start, int64_t n_walkers, int64_t length,
+                                            double p, double q, int max_trials, uint64_t seed, int64_t *walks,
+                                            int32_t *fallback_steps, int *flags);
+
 #ifdef __cplusplus
 }
 #endif
