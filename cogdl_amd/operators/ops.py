@@ -31,7 +31,7 @@ _OPS_WMUL = 3  # COGDL_HIP_GSPMM_WMUL: (x * weight) * efeat, autograd's rounding
 class EdgePlan:
     """Destination-sorted view of an edge list: rowptr int32 [n+1], perm int32 [E] (sorted position -> edge id; stable),
     sorted (perm is the identity)."""
-    __slots__ = ("rowptr", "perm", "sorted", "n", "keep", "_col_key", "_col_src", "_colind", "uses", "_skewed", "_xcd_key", "_xcd", "_xcd_builds")
+    __slots__ = ("rowptr", "perm", "sorted", "n", "keep", "_col_key", "_col_src", "_colind", "uses", "skewed", "_xcd_key", "_xcd", "_xcd_builds")
 
     def __init__(self, dst, n):
         from ..graph_build import coo2csr_index
@@ -44,9 +44,7 @@ class EdgePlan:
         self.n = n
         self.keep = dst  # pins the key tensor: its data_ptr cannot be recycled while the plan lives
         self._col_key, self._col_src, self._colind = None, None, None
-        self.uses, self._skewed, self._xcd_key, self._xcd, self._xcd_builds = 0, None, None, None, 0
-
-    XCD_MIN_COLUMNS = 65  # (narrower rows: the plan's launch measured 8-15 % SLOWER than the ordinary one, below)
+        self.uses, self.skewed, self._xcd_key, self._xcd, self._xcd_builds = 0, None, None, None, 0
 
     def xcd(self, colind, k):
         """The XCD-partitioned, length-ordered plan of this view (cogdl_amd/xcdplan.py) for the launch that walks `colind` (int32,
@@ -58,26 +56,16 @@ class EdgePlan:
         327 -> 355 and F = 32 202 -> 231 us: rows of more than 64 columns only."""
         from .. import xcdplan
 
-        nnz = self.perm.numel()
-        if xcdplan.MODE == "off" or nnz == 0:
+        if not xcdplan.edge_list_wanted(self, k):
             return None
-        if xcdplan.MODE != "force":
-            if self.uses < 2 or nnz < xcdplan.ORDERED_MIN_EDGES or k < self.XCD_MIN_COLUMNS:
-                return None
-            if self._skewed is None:
-                if torch.cuda.is_current_stream_capturing():
-                    return None
-                self._skewed = xcdplan.skewed(self.rowptr)
-            if not self._skewed:
-                return None
         key = tensor_key(colind)
         if key != self._xcd_key or self._xcd is None:
             if torch.cuda.is_current_stream_capturing():  # (the build reads sizes back: never inside a capture)
                 return None
-            if self._xcd_builds >= 4 and xcdplan.MODE != "force":
+            if self._xcd_builds >= 4 and not xcdplan.forced():
                 return None  # (a caller that pairs this index with ever new partner tensors: no plan build per call)
             self._xcd_builds += 1
-            split = int(_lib.hip().cogdl_hip_exact_row_edges(nnz))
+            split = int(_lib.hip().cogdl_hip_exact_row_edges(self.perm.numel()))
             plan = xcdplan.build(self.rowptr, colind, eid_base=None if self.sorted else self.perm, split=split)
             self._xcd_key, self._xcd = key, (plan, colind)  # (colind kept: pins the key's address)
         return self._xcd[0]

@@ -21,7 +21,7 @@ import torch
 from .. import _lib
 from .. import plan as _plan
 from .. import xcdplan
-from ..plan import PLANS, Fingerprint, fingerprint_of, csr2csc, gather_rows
+from ..plan import PLANS, fingerprint_of, csr2csc, gather_rows
 
 _lib.hip()  # fail at import if the HIP library is missing (no silent `csrspmm = None`)
 
@@ -141,35 +141,6 @@ def csr_spmm_xcd_raw(xplan, val, x, out=None):
     return out
 
 
-SPLIT_16 = 256  # (= xcdplan.SPLIT: 16-bit csr_spmm and the fused GAT operator share one plan per structure)
-
-
-def _xcd_split(rowptr, colind, x, fp=None):
-    """Does this csr_spmm launch take an XCD-partitioned plan (cogdl_amd/xcdplan.py), and cut at which row length?
-    -> None (no plan) or the split.
-      fp32    hub-heavy structures over cache-sized tables (xcdplan.wanted): yes, with split = the exact-row bound of the
-              ordinary path (cogdl_hip_exact_row_edges(nnz)) -- rows up to that length stay whole and bit-identical to the
-              reference loop, as before; only the rows the ordinary path already re-associates (its long-row pieces) are cut by
-              owner XCD instead of into contiguous chunks.  Measured on the Reddit-shaped graph, F = 64: see
-              profiles/r06_xcd_spmm_fp32.txt.
-      16-bit  the same structures and tables, cut at SPLIT_16 = 256 edges (no bit-exact contract to keep).  Measured on the
-              Reddit-shaped graph (profiles/r06_xcd_spmm_split.txt): bf16 F = 64 1524 -> 1316 us, F = 128 3241 -> 2291 us; at
-              split 64 / 1024: 1386 / 1345 us.  (Before the hub rows' part records were merged by whole workgroups -- rowreduce.h:
-              rowreduce_vcombine_kernel -- the same plan LOST: 1512 -> 1638 us, profiles/r06_xcd_quick.txt.)"""
-    if x.dim() != 2 or x.dtype not in _lib.DTYPE_CODE:
-        return None
-    m, nnz = rowptr.numel() - 1, colind.numel()
-    if xcdplan.MODE == "force":
-        return xcdplan.SPLIT if xcdplan.wanted(m, nnz, x.shape[0], x.shape[1] * x.element_size()) else None
-    if xcdplan.wanted(m, nnz, x.shape[0], x.shape[1] * x.element_size()):
-        return int(_lib.hip().cogdl_hip_exact_row_edges(nnz)) if x.dtype == torch.float32 else SPLIT_16
-    # skewed structures of any size, when the structure's fingerprint is on the host already (xcdplan.ordered_wanted): cut at the
-    # exact-row bound whatever the dtype (rows up to it stay whole and sequential, as in the ordinary launch)
-    if xcdplan.ordered_wanted(fp, rowptr, m, nnz, x.shape[0], x.shape[1] * x.element_size()):
-        return int(_lib.hip().cogdl_hip_exact_row_edges(nnz))
-    return None
-
-
 def csr_sddmm_raw(rowptr, colind, d1, d2):
     """out[e] = <d1[row(e)], d2[col[e]]>  (fp32)."""
     dev = _lib.require_cuda(rowptr, colind, d1, d2)
@@ -194,36 +165,14 @@ class SPMMFunction(torch.autograd.Function):
         # kernel, not behind the SpMM).
         rowptr, colind = _lib.csr_structure(rowptr, colind)  # validated + contiguous before anything reads raw pointers
         ctx.transient = _plan.transient()  # (the dense operand is checked by csr_spmm_raw)
-        taped = _plan._TAPE is not None and not ctx.transient
-        ctx.xcd = None if taped else _xcd_split(rowptr, colind, feat)
-        memo = getattr(rowptr, "_cogdl_amd_struct", None) is not None
         if ctx.transient:
             ctx.fp = None
-        elif ctx.needs_input_grad[2] or ctx.xcd is not None or memo or taped:
+        elif ctx.needs_input_grad[2] or _plan.memoised(rowptr) or _plan.taping():
             ctx.fp = fingerprint_of(rowptr, colind, feat.shape[0])
         else:
             ctx.fp = _plan.known_fingerprint(rowptr, colind, feat.shape[0])  # (never hashes: inference calls stay as they were)
-        xplan = None
-        if taped:
-            # cogdl_amd.graphs.capture: the recorded eager run waits for the structure's key and decides as a call with a known
-            # fingerprint would; the capture takes the recorded decision (nothing is hashed or read back while capturing)
-            def decide():
-                ctx.fp.key()
-                split = _xcd_split(rowptr, colind, feat, ctx.fp)
-                return split, (xcdplan.csr_plan(ctx.fp, rowptr, colind, split) if split is not None else None)
-
-            ctx.xcd, xplan = _plan.taped_choice("csr_spmm.forward", decide)
-        elif ctx.xcd is None and ctx.fp is not None:
-            # a memoised fingerprint (install(structure_memo=True)): its key costs ONE wait per structure, after which skewed
-            # structures of any size take a plan -- deterministically, from the first call on.  The identity memo (the same
-            # index tensor objects as an earlier call, plan.fingerprint_of) has its key once a backward pass has asked for it.
-            if memo and ctx.fp.event is not None:
-                ctx.fp.key()
-            if ctx.fp._key is not None:
-                ctx.xcd = _xcd_split(rowptr, colind, feat, ctx.fp)
-        if ctx.xcd is not None:
-            if xplan is None:
-                xplan = xcdplan.csr_plan(ctx.fp, rowptr, colind, ctx.xcd)
+        ctx.xcd, xplan = xcdplan.spmm_forward(ctx.fp, rowptr, colind, feat)
+        if xplan is not None:
             out = csr_spmm_xcd_raw(xplan, edge_weight_csr, feat)
         else:
             out = csr_spmm_raw(rowptr, colind, edge_weight_csr, feat)
@@ -245,15 +194,7 @@ class SPMMFunction(torch.autograd.Function):
                 grad_feat = csr_spmm_raw(plan.colptr, plan.rowind, w_t, grad_out)
             else:
                 plan = PLANS.get(ctx.fp, rowptr, colind, ctx.n_src)
-                # (the key is known here -- PLANS.get has waited for the hash: the transpose of a skewed structure takes a plan
-                #  whether or not the forward call could -- from its SECOND sighting on: a structure that never comes back, a
-                #  sampled block passed without plan.transient_structures(), must not pay a plan build of milliseconds)
-
-                def decide():
-                    split_t = _xcd_split(plan.colptr, plan.rowind, grad_out, ctx.fp if (ctx.xcd is not None or getattr(plan, "sightings", 1) > 1) else None)
-                    return split_t, (xcdplan.csc_plan(ctx.fp, plan, split_t) if split_t is not None else None)
-
-                split_t, xplan_t = _plan.taped_choice("csr_spmm.backward", decide)
+                split_t, xplan_t = xcdplan.spmm_backward(ctx.fp, plan, grad_out, ctx.xcd is not None)
                 if split_t is not None:
                     # (w stays in CSR order: the plan of the transpose maps its positions through the transpose's perm)
                     grad_feat = csr_spmm_xcd_raw(xplan_t, w, grad_out)

@@ -172,6 +172,11 @@ def set_tape(tape):
     _TAPE = tape
 
 
+def taping():
+    """Is a tape set: the recorded eager run of cogdl_amd.graphs.capture, or the capture that replays it?"""
+    return _TAPE is not None
+
+
 def recording():
     """Is this the eager run whose lookups cogdl_amd.graphs.capture() records?  (It may wait for a structure hash: the run is
     not captured -- so every launch of a captured step can be given the plan a call with a known fingerprint would take.)"""
@@ -280,6 +285,11 @@ class Fingerprint:
             self._key = self.meta + (int(self.host.sum()),)  # int64 sum wraps: the sum modulo 2^64
         return self._key
 
+    def wait(self):
+        """Wait for the key if a hash is in flight (none is behind a Fingerprint made while a capture replays its tape)."""
+        if self.event is not None:
+            self.key()
+
     def __del__(self):
         # Back to the pool once the kernel that writes the buffer is known to be done; otherwise the pair is parked
         # on _PENDING (keeping the pinned block allocated) until a later call finds its event complete.
@@ -308,6 +318,11 @@ _IDENT_MAX = 16
 
 def _ident_state(rowptr, colind):
     return (rowptr._version, colind._version, rowptr.data_ptr(), colind.data_ptr(), rowptr.numel(), colind.numel())
+
+
+def memoised(rowptr):
+    """Does `rowptr` come from a Graph under install(structure_memo=True) (cogdl_amd/structure_memo.py)?"""
+    return getattr(rowptr, "_cogdl_amd_struct", None) is not None
 
 
 def known_fingerprint(rowptr, colind, n_cols):

@@ -85,12 +85,6 @@ class _StructIndex(torch.Tensor):
         return cached
 
 
-def lookup(rowptr, colind, n_cols):
-    """The memoised Fingerprint for an operator call's (rowptr, colind), or None (then the caller hashes as before)."""
-    memo = getattr(rowptr, "_cogdl_amd_struct", None)
-    return memo.fingerprint(rowptr, colind, n_cols) if memo is not None else None
-
-
 def _wrap(adj, base, which):
     if not torch.is_tensor(base) or base.dtype != torch.int64 or not base.is_cuda:
         return base  # CPU graphs: the reference's own path, untouched

@@ -9,9 +9,10 @@ order in which the hardware hands workgroups to them.  Shorter rows stay whole. 
 GE-SpMM kernels, cogdl/operators/spmm/spmm_kernel.cu:192-512, know one L2).
 
 The plan is a property of the STRUCTURE: built once (a handful of sorts over the edge list, torch on the device: ~0.2 s at
-1.1e8 edges), cached under the structure's content fingerprint next to the transpose (cogdl_amd/plan.py).  When it is used:
-`wanted()` -- hub-heavy launches over cache-sized tables -- for the fused GAT operator and 16-bit csr_spmm; fp32 csr_spmm keeps
-its bit-exact rows unless asked (`MODE = "force"` / COGDL_AMD_XCD=force), because a row cut into sub-rows is re-associated.
+1.1e8 edges), cached under the structure's content fingerprint next to the transpose (cogdl_amd/plan.py).  WHEN a launch runs
+over one, and cut at which row length, is decided by the policy at the end of this file, for every operator that can take a plan.
+fp32 csr_spmm is cut at the exact-row bound of its ordinary launch: rows up to it stay whole and bit-identical, only the longer
+rows -- which the ordinary launch re-associates too -- are cut by owner.  `MODE` (COGDL_AMD_XCD) overrides the rules for A/B runs.
 """
 import collections
 import ctypes
@@ -171,7 +172,7 @@ def wanted(m, nnz, n_src, row_bytes):
     forward + backward: H = 8 x F = 8 bf16 (128-byte rows, 30 MB) 7.31 -> 5.66 ms, fp32 (60 MB) 11.83 -> 7.73 ms; H = 1 x
     F = 48 bf16 (96-byte rows, 22 MB: one head per lane group, bound by instruction issue, not by the gathers) 6.07 -> 5.97 ms
     without and 6.56 -> 6.93 ms with dropout -- not taken (the operator pads such rows to 128 bytes: fused_gat._padded_width).
-    Which operators ask: the fused GAT operator, and csr_spmm in fp32 (cut at its exact-row bound: operators/spmm.py)."""
+    Which operators ask: the policy at the end of this file."""
     if MODE == "off" or _plan.transient():
         return False
     if n_src >= (1 << 24) or n_src * row_bytes >= (1 << 32):  # (the plan kernels address the table with 24 x 24 -> 32-bit offsets)
@@ -188,19 +189,15 @@ _SKEW = {}
 
 
 def ordered_wanted(fp, rowptr, m, nnz, n_src, row_bytes):
-    """The second way into a plan (round 6): a SKEWED structure of any size whose fingerprint is ALREADY KNOWN on the host --
-    memoised with the Graph (install(structure_memo=True)) or by tensor identity (plan.fingerprint_of), or a backward pass, which
-    has waited for the hash anyway (the operators take it from the structure's second sighting on: plan.CscPlan.sightings).  What a
+    """The second way into a plan (round 6): a SKEWED structure of any size whose fingerprint is ALREADY KNOWN on the host (who
+    waits for it, and when a key counts as known: the policy at the end of this file).  What a
     plan buys there is its slot order: an XCD's virtual rows by decreasing length, so that the lane groups of a wave walk rows
     of one length, and hub rows as pieces merged by rowreduce_vcombine_kernel.  Measured on the arxiv-sized R-MAT graph (max
     degree 10^4; tools/exp/small_plan_ab.py, profiles/r06_small_plan_ab.txt), ordinary launch -> plan cut at the exact-row
     bound: fp32 F = 128 183 -> 144 us, F = 64 100 -> 63 us, F = 40 103 -> 60 us; bf16 134 -> 68, 96 -> 44, 95 -> 47 us; on
     the uniform graph of the same size +-3 % -- hence the skew test (one pass over the degrees per structure, cached): the
     share of lane-slots that eight consecutive rows fill, 0.73 on the uniform graph, 0.32 on the R-MAT one.
-    A forward call whose hash is still in flight keeps the ordinary launch: waiting would drain the stream.
-    Under cogdl_amd.graphs.capture the operators ask through plan.taped_choice: the recorded eager run waits for the key (it is
-    not captured), the capture replays its decisions -- every launch of a captured step runs over the plan a known structure
-    takes, forward calls included."""
+    A forward call whose hash is still in flight keeps the ordinary launch: waiting would drain the stream."""
     if MODE == "off" or _plan.transient() or fp is None or getattr(fp, "_key", None) is None:
         return False
     if nnz < ORDERED_MIN_EDGES or n_src >= (1 << 24) or n_src * row_bytes >= (1 << 32) or row_bytes >= (1 << 22):
@@ -264,3 +261,112 @@ def csc_plan(fp, csc, split=None):
     """The plan of the transpose (a CscPlan): per-edge operands are indexed through its perm."""
     split = SPLIT if split is None else int(split)
     return XPLANS.get(("csc", split, PIECE) + fp.key(), lambda: build(csc.colptr, csc.rowind, eid_base=csc.perm, split=split))
+
+
+# ------------------------------------------------------------------------------------------------------------ the policy
+# Does a launch run over a plan, and cut at which row length?  The operators pass facts and launch what comes back (the rules in
+# prose: DESIGN.md).  H = wanted(): needs no key.  S = ordered_wanted(): a Fingerprint whose hash is in flight gets a no.  E =
+# cogdl_hip_exact_row_edges(nnz).  Decisions go through plan.taped_choice: a capture replays what its recorded eager run decided.
+
+
+def forced():
+    return MODE == "force"
+
+
+def spmm_split(fp, rowptr, m, nnz, x):
+    """csr_spmm, either direction: the row length to cut at, or None (the ordinary launch).  fp: the structure's Fingerprint if its
+    key counts as known to this call, else None.
+      fp32    H: cut at E -- rows up to E stay whole and bit-identical to the reference loop; only the rows the ordinary path
+              already re-associates (its long-row pieces) are cut by owner XCD instead of into contiguous chunks.  Measured on the
+              Reddit-shaped graph, F = 64: see profiles/r06_xcd_spmm_fp32.txt.
+      16-bit  H: cut at SPLIT (no bit-exact contract to keep; one plan per structure with the fused GAT operator).  Measured on the
+              Reddit-shaped graph (profiles/r06_xcd_spmm_split.txt): bf16 F = 64 1524 -> 1316 us, F = 128 3241 -> 2291 us; at
+              split 64 / 1024: 1386 / 1345 us.  (Before the hub rows' part records were merged by whole workgroups -- rowreduce.h:
+              rowreduce_vcombine_kernel -- the same plan LOST: 1512 -> 1638 us, profiles/r06_xcd_quick.txt.)
+      else S  cut at E whatever the dtype (rows up to it stay whole and sequential, as in the ordinary launch)."""
+    if x.dim() != 2 or x.dtype not in _lib.DTYPE_CODE:
+        return None
+    n_src, row_bytes = x.shape[0], x.shape[1] * x.element_size()
+    hub = wanted(m, nnz, n_src, row_bytes)
+    if MODE == "force":  # (kept as is: S is not consulted, and fp32 is cut at SPLIT too)
+        return SPLIT if hub else None
+    if hub and x.dtype != torch.float32:
+        return SPLIT
+    return int(_lib.hip().cogdl_hip_exact_row_edges(nnz)) if hub or ordered_wanted(fp, rowptr, m, nnz, n_src, row_bytes) else None
+
+
+def spmm_forward(fp, rowptr, colind, x):
+    """SPMMFunction.forward -> (split, plan) or (None, None).  fp: the call's Fingerprint; None where the call hashed nothing (no
+    gradient wanted, no memo knows the tensors): a hub-heavy launch then hashes here, for its plan's key.  A memoised structure
+    waits for its key (ONCE per structure), and so does the recorded eager run of cogdl_amd.graphs.capture (kept as is: under ANY
+    tape, where gat_forward asks for a recording one); the identity memo has its key once a backward pass has asked."""
+    if _plan.transient():
+        return None, None
+
+    def decide():
+        if fp is not None and (_plan.taping() or _plan.memoised(rowptr)):
+            fp.wait()
+        split = spmm_split(fp, rowptr, rowptr.numel() - 1, colind.numel(), x)
+        if split is None:
+            return None, None
+        return split, csr_plan(fp if fp is not None else _plan.fingerprint_of(rowptr, colind, x.shape[0]), rowptr, colind, split)
+
+    return _plan.taped_choice("csr_spmm.forward", decide)
+
+
+def spmm_backward(fp, csc, grad_out, took_plan):
+    """SPMMFunction.backward over the transpose `csc` (a plan.CscPlan) -> (split, plan) or (None, None).  PLANS.get has waited for
+    the hash, but the key counts only after a plan forward or from the structure's SECOND sighting on: no plan build for one-offs."""
+    def decide():
+        split = spmm_split(fp if (took_plan or csc.sightings > 1) else None, csc.colptr, csc.colptr.numel() - 1,
+                           csc.rowind.numel(), grad_out)
+        return split, (csc_plan(fp, csc, split) if split is not None else None)
+
+    return _plan.taped_choice("csr_spmm.backward", decide)
+
+
+def gat_forward(fp, rowptr, colind, n_src, row_bytes):
+    """FusedGATFunction.forward -> the structure's plan (cut at SPLIT) or None.  row_bytes: None for an operand the kernels refuse.
+    H; else S -- a memoised structure and the recorded eager run of cogdl_amd.graphs.capture wait for the key."""
+    def decide():
+        if row_bytes is None:
+            return None
+        m, nnz = rowptr.numel() - 1, colind.numel()
+        if not wanted(m, nnz, n_src, row_bytes):
+            if _plan.memoised(rowptr) or _plan.recording():  # (kept as is: a RECORDING tape, where spmm_forward asks for any)
+                fp.wait()
+            if not ordered_wanted(fp, rowptr, m, nnz, n_src, row_bytes):
+                return None
+        return csr_plan(fp, rowptr, colind)
+
+    return _plan.taped_choice("fused_gat.forward", decide)
+
+
+def gat_backward(fp, csc, rowptr, colind, n_src, row_bytes, took_plan):
+    """FusedGATFunction.backward -> (plan of the structure, plan of its transpose `csc`) or None: the forward ran the plan kernels,
+    or S from the structure's second sighting on (see spmm_backward).  (kept as is: H is not asked again)"""
+    def decide():
+        if took_plan or (csc.sightings > 1 and ordered_wanted(fp, rowptr, rowptr.numel() - 1, colind.numel(), n_src, row_bytes)):
+            return csr_plan(fp, rowptr, colind), csc_plan(fp, csc)
+        return None
+
+    return _plan.taped_choice("fused_gat.backward", decide)
+
+
+EDGE_LIST_MIN_COLUMNS = 65  # (narrower rows: the plan's launch measured 8-15 % SLOWER than the ordinary one: EdgePlan.xcd)
+
+
+def edge_list_wanted(edges, k):
+    """gspmm of k columns over a memoised edge list (operators/ops.py: EdgePlan.xcd): skewed lists from their second use on."""
+    nnz = edges.perm.numel()
+    if MODE == "off" or nnz == 0:
+        return False
+    if MODE == "force":
+        return True
+    if edges.uses < 2 or nnz < ORDERED_MIN_EDGES or k < EDGE_LIST_MIN_COLUMNS:
+        return False
+    if edges.skewed is None:
+        if torch.cuda.is_current_stream_capturing():  # (the skew test reads back: never inside a capture)
+            return False
+        edges.skewed = skewed(edges.rowptr)
+    return edges.skewed
