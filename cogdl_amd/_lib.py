@@ -128,6 +128,9 @@ HIP_SIGNATURES = {
     # random walks (csrc/walk.hip)
     "cogdl_hip_random_walk": ([_vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _u64, _vp, _vp, _vp], _i32),
     "cogdl_hip_node2vec_walk": ([_vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _f64, _i32, _u64, _vp, _vp, _vp, _vp], _i32),
+    # top-k personalised PageRank (csrc/ppr.hip)
+    "cogdl_hip_ppr_topk_workspace_bytes": ([_i64, _i64, _i64, _f64, _f64, _i64], _sz),
+    "cogdl_hip_ppr_topk": ([_vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _f64, _i64] + [_vp] * 6 + [_sz, _vp], _i32),
 }
 
 MAX_SEGMENTS = 64  # COGDL_HIP_MAX_SEGMENTS
@@ -149,6 +152,8 @@ HOST_SIGNATURES = {
     "cogdl_host_csr_spmm_f32_i64": ([_vp] * 5 + [_i64, _i64, _i32], _i32),
     "cogdl_host_random_walk": ([_vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _u64, _vp, _vp], _i32),
     "cogdl_host_node2vec_walk": ([_vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _f64, _i32, _u64, _vp, _vp, _vp], _i32),
+    "cogdl_host_ppr_plan": ([_i64, _i64, _i64, _f64, _f64, _vp], _i32),
+    "cogdl_host_ppr_topk": ([_vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _f64, _i64] + [_vp] * 5, _i32),
 }
 
 EUNSUPPORTED = 7  # COGDL_HIP_EUNSUPPORTED

@@ -37,7 +37,7 @@ _finder = None
 
 
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
-            metis=False, big_graphs=False, torch_sparse=False, random_walk=False):
+            metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -65,6 +65,12 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     cogdl_amd.random_walk_compat.RandomWalker: Graph.random_walk / random_walk_with_restart and the unsupervised sampler's
     positive pairs run on the library's walk operators (HIP kernels for a graph on the GPU, the OpenMP host twin otherwise)
     instead of the reference's numba / interpreted Python loop.
+    ppr=True rebinds `ppr_topk`, `topk_ppr_matrix` and `build_topk_ppr_matrix_from_data` in cogdl.utils.ppr_utils and the
+    by-name copies in cogdl.wrappers.data_wrapper.node_classification.pprgo_dw and cogdl.models.nn.mvgrl (opt-in: the scores
+    are those of a deterministic push order, within eps * deg of the reference's) to cogdl_amd.ppr_compat: the top-k PPR
+    matrix of pprgo and mvgrl comes from the library's PPR operator (HIP kernel when a GPU is visible, the OpenMP host twin
+    otherwise).  Where cogdl.utils.ppr_utils cannot be imported (numba missing), cogdl_amd.ppr_compat is registered under
+    that name, so the two models import at all.
     linear=True additionally routes torch.nn.functional.linear -- i.e. the unchanged nn.Linear inside every CogDL
     layer -- through cogdl_amd.linear (hand-written MFMA weight gradient for full-graph shapes)."""
     global _finder
@@ -128,6 +134,8 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
             sys.modules["torch_sparse"] = importlib.import_module("cogdl_amd.torch_sparse_compat")
     if random_walk:
         _rebind_random_walker()
+    if ppr:
+        _rebind_ppr()
     su = sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):
@@ -202,7 +210,50 @@ def _rebind_random_walker():
             mod.RandomWalker = RandomWalker
 
 
+_PPR_NAMES = ("ppr_topk", "topk_ppr_matrix", "build_topk_ppr_matrix_from_data")
+_PPR_UTILS = "cogdl.utils.ppr_utils"
+_PPR_HOLDERS = ("cogdl.wrappers.data_wrapper.node_classification.pprgo_dw", "cogdl.models.nn.mvgrl")
+
+
+def _rebind_ppr():
+    """cogdl.utils.ppr_utils is imported (or, where numba is missing, served by cogdl_amd.ppr_compat under that name), then
+    the three functions are rebound there and in the two modules that copied one by name; the originals are kept for
+    uninstall()."""
+    from . import ppr_compat
+
+    _import_target("cogdl.utils", "ppr")
+    try:
+        importlib.import_module(_PPR_UTILS)
+    except ImportError:  # numba missing: the reference module cannot load
+        sys.modules[_PPR_UTILS] = ppr_compat
+        sys.modules["cogdl.utils"].ppr_utils = ppr_compat
+    for name in _PPR_HOLDERS:  # (before anything is rebound: they copy the names they will get back at uninstall())
+        _import_target(name, "ppr")
+    for name in (_PPR_UTILS,) + _PPR_HOLDERS:
+        mod = sys.modules[name]
+        if mod is ppr_compat:
+            continue
+        for fn in _PPR_NAMES:
+            cur = getattr(mod, fn, None)
+            if cur is None or cur is getattr(ppr_compat, fn):
+                continue
+            mod.__dict__.setdefault("_cogdl_amd_orig_ppr", {}).setdefault(fn, cur)
+            setattr(mod, fn, getattr(ppr_compat, fn))
+
+
 def uninstall():
+    for name in (_PPR_UTILS,) + _PPR_HOLDERS:
+        mod = sys.modules.get(name)
+        if mod is None:
+            continue
+        if getattr(mod, "__name__", "") == "cogdl_amd.ppr_compat":  # registered in place of the module that cannot load
+            del sys.modules[name]
+            utils = sys.modules.get("cogdl.utils")
+            if utils is not None and getattr(utils, "ppr_utils", None) is mod:
+                del utils.ppr_utils
+            continue
+        for fn, orig in mod.__dict__.pop("_cogdl_amd_orig_ppr", {}).items():
+            setattr(mod, fn, orig)
     for name in _RANDOM_WALKER_MODULES:
         mod = sys.modules.get(name)
         if mod is not None and "_cogdl_amd_orig_random_walker" in mod.__dict__:

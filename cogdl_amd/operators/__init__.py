@@ -8,6 +8,7 @@
     sample.py        sample_adj_c, subgraph_c, coo2csr_cpu, coo2csr_cpu_index  (cogdl/operators/sample.py)
 
     walk.py          random_walk, node2vec_walk (also exported here)   (cogdl/utils/sampling.py, models/emb/node2vec.py)
+    ppr.py           topk_ppr, full_ppr (also exported here)           (cogdl/utils/ppr_utils.py)
 
     ops.py           scatter_add, op_aggr, s_*_e_sum / s_*_e_mean (fused HIP), s_*_e, s_*_t   (cogdl/operators/ops.py)
 
@@ -21,4 +22,8 @@ def __getattr__(name):
         from . import walk
 
         return getattr(walk, name)
+    if name in ("topk_ppr", "full_ppr"):
+        from . import ppr
+
+        return getattr(ppr, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -772,6 +772,39 @@ COGDL_API int cogdl_hip_node2vec_walk(const int64_t *indptr, const int64_t *indi
                             const int64_t *start, int64_t n_walkers, int64_t length, double p, double q, int max_trials,
                             uint64_t seed, int64_t *walks, int32_t *fallback_steps, int *flags, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Top-k personalised PageRank by forward push (csrc/ppr.hip), replacing the numba / interpreted loop of
+ * cogdl/utils/ppr_utils.py:8-48.  int64 indptr[num_nodes + 1] / indices[num_edges] on the device, deg[u] =
+ * indptr[u + 1] - indptr[u], int64 sources[S].  Host twin with identical results: cogdl_host_ppr_topk.
+ *   Process     per source s: r[s] = alpha; pushing u does res = r[u]; p[u] += res; r[u] = 0; r[v] += (1 - alpha) * res /
+ *               deg[u] for every entry v of u's row.  Round 0 pushes s; round t pushes exactly the nodes with r > 0 and
+ *               r >= alpha * eps * deg at its start; the process ends when there are none.  (The reference pushes in LIFO
+ *               order, so its values differ within the bound below.)
+ *   Arithmetic  r and p are unsigned 64-bit multiples of 2^-62 and the share is floored (csrc/ppr_fixed.h), so additions
+ *               commute: the result is a function of the inputs alone, equal from run to run and equal to the host twin's.
+ *   Guarantees  on return r[v] < alpha * eps * deg[v] for every v; p never exceeds the exact PPR row pi_s, and on a
+ *               symmetric structure pi_s[t] - p[t] < eps * deg[t] + 2^-24 (2^-24 bounds the flooring loss).
+ *   Accepted    alpha in (0, 1), eps > 0, alpha * eps >= 2^-20, and 4 (E + budget + 2) / alpha * 2^-62 < 2^-24 with
+ *               budget = floor(2^62 / floor(alpha * eps * 2^62)) + 1; otherwise COGDL_HIP_EINVAL / COGDL_HIP_ERANGE and the
+ *               workspace query returns 0.
+ *   Output      of the touched nodes with p > 0 the topk largest by p, ties by smaller node id, in that order:
+ *               nbr int64[S, topk] (unused slots -1), val float32[S, topk] (p rounded to nearest; unused 0),
+ *               count int32[S].  stats: NULL, or int32[S, 2] receiving rounds and touched nodes per source.
+ *   Tables      a source touches at most 1 + deg[s] + budget nodes; max_source_degree must bound deg[s] over the sources
+ *               (the tables are sized from it; a value that is too small raises bit 3, nothing overflows).
+ *   *flags      device int, zeroed by the call: bit 0 a source id outside [0, num_nodes), bit 1 a neighbour id outside,
+ *               bit 2 a row of indptr that is not a range inside [0, num_edges], bit 3 table full, bit 4 round bound
+ *               reached.  A source that meets one ends with count 0 and an empty row; nothing is read out of bounds and
+ *               every device loop is bounded.  Non-zero marks an invalid result.
+ *   The call enqueues on `stream`, allocates nothing and does not synchronise; ws must hold
+ *   cogdl_hip_ppr_topk_workspace_bytes(...) bytes (16-byte aligned) and is bounded whatever S is (a persistent grid). */
+COGDL_API size_t cogdl_hip_ppr_topk_workspace_bytes(int64_t num_nodes, int64_t num_edges, int64_t max_source_degree,
+                                          double alpha, double eps, int64_t n_sources);
+COGDL_API int cogdl_hip_ppr_topk(const int64_t *indptr, const int64_t *indices, int64_t num_nodes, int64_t num_edges,
+                       const int64_t *sources, int64_t n_sources, int64_t max_source_degree, double alpha, double eps,
+                       int64_t topk, int64_t *nbr, float *val, int32_t *count, int32_t *stats, int *flags, void *ws,
+                       size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

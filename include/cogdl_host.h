@@ -102,6 +102,22 @@ COGDL_HOST_API int cogdl_host_node2vec_walk(const int64_t *indptr, const int64_t
                                             double p, double q, int max_trials, uint64_t seed, int64_t *walks,
                                             int32_t *fallback_steps, int *flags);
 
+/* Top-k personalised PageRank by forward push; the host twin of cogdl_hip_ppr_topk (include/cogdl_hip.h, where the contract
+ * is spelled out): same arguments minus workspace and stream, and for equal inputs EXACTLY the arrays the GPU returns --
+ * both run the fixed-point arithmetic of csrc/ppr_fixed.h in the same synchronous rounds.  OpenMP over the sources; the
+ * result does not depend on the number of threads.  *flags (host int) as in the GPU entry point.
+ * cogdl_host_ppr_plan validates (alpha, eps) for a graph size and reports what both twins derive from them:
+ * out[0] = push budget floor(2^62 / thr) + 1, out[1] = table slots, out[2] = round bound, out[3] = 1 if the GPU keeps a
+ * table of that size in LDS.  COGDL_HOST_EINVAL: a parameter outside its domain (alpha in (0, 1), eps > 0);
+ * COGDL_HOST_ERANGE: alpha * eps < 2^-20, or the proven rounding loss 4 (E + budget + 2) / alpha * 2^-62 is not below
+ * 2^-24, or the table would exceed 2^23 slots. */
+COGDL_HOST_API int cogdl_host_ppr_plan(int64_t num_nodes, int64_t num_edges, int64_t max_source_degree, double alpha,
+                                       double eps, int64_t *out);
+COGDL_HOST_API int cogdl_host_ppr_topk(const int64_t *indptr, const int64_t *indices, int64_t num_nodes, int64_t num_edges,
+                                       const int64_t *sources, int64_t n_sources, int64_t max_source_degree, double alpha,
+                                       double eps, int64_t topk, int64_t *nbr, float *val, int32_t *count, int32_t *stats,
+                                       int *flags);
+
 #ifdef __cplusplus
 }
 #endif
