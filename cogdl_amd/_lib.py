@@ -131,6 +131,10 @@ HIP_SIGNATURES = {
     # top-k personalised PageRank (csrc/ppr.hip)
     "cogdl_hip_ppr_topk_workspace_bytes": ([_i64, _i64, _i64, _f64, _f64, _i64], _sz),
     "cogdl_hip_ppr_topk": ([_vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _f64, _i64] + [_vp] * 6 + [_sz, _vp], _i32),
+    # skip-gram with negative sampling (csrc/sgns.hip)
+    "cogdl_hip_sgns_init": ([_vp, _vp, _i64, _i32, _u64, _vp], _i32),
+    "cogdl_hip_sgns_train": ([_vp, _i64, _i64, _i64, _i32, _i32, _i32, _i64, _f64, _f64, _vp, _vp, _vp, _u64, _i32, _i64,
+                              _vp, _vp, _vp, _vp], _i32),
 }
 
 MAX_SEGMENTS = 64  # COGDL_HIP_MAX_SEGMENTS
@@ -154,6 +158,9 @@ HOST_SIGNATURES = {
     "cogdl_host_node2vec_walk": ([_vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _f64, _i32, _u64, _vp, _vp, _vp], _i32),
     "cogdl_host_ppr_plan": ([_i64, _i64, _i64, _f64, _f64, _vp], _i32),
     "cogdl_host_ppr_topk": ([_vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _f64, _i64] + [_vp] * 5, _i32),
+    "cogdl_host_sgns_init": ([_vp, _vp, _i64, _i32, _u64], _i32),
+    "cogdl_host_sgns_train": ([_vp, _i64, _i64, _i64, _i32, _i32, _i32, _i64, _f64, _f64, _vp, _vp, _vp, _u64, _i32,
+                               _vp, _vp, _vp, _vp, _i64, _vp], _i32),
 }
 
 EUNSUPPORTED = 7  # COGDL_HIP_EUNSUPPORTED

@@ -1,0 +1,59 @@
+"""Unsupervised node embeddings without leaving the device: walks from the library's walk operators, trained by the
+library's skip-gram operator -- what the reference's DeepWalk / Node2vec do through networkx and gensim
+(cogdl/models/emb/deepwalk.py:54-110, node2vec.py:72-140).
+
+    deepwalk(graph_or_csr, dim, walk_length, walk_num, window, epochs)      -> float32 [N, dim]
+    node2vec(graph_or_csr, dim, walk_length, walk_num, window, epochs, p, q) -> float32 [N, dim]
+
+`graph_or_csr` is a cogdl Graph (its row_indptr / col_indices are used on the device they live on) or an
+(indptr, indices) pair of int64 tensors.  Each of the walk_num passes starts one walk at every node, in an order shuffled
+per pass (as the reference does); the passes' rows follow each other, which is the order the trainer consumes them in.
+Differences from the reference: the draws come from Philox, not from numpy's / gensim's generators; at a node without
+out-neighbours the walker stays (the reference ends the walk); node2vec ignores edge weights.
+"""
+import torch
+
+from .operators.sgns import skipgram
+from .operators.walk import _seed, node2vec_walk, random_walk
+
+
+def _csr(graph_or_csr):
+    if isinstance(graph_or_csr, (tuple, list)):
+        indptr, indices = graph_or_csr
+    else:
+        indptr, indices = graph_or_csr.row_indptr, graph_or_csr.col_indices
+    indptr, indices = torch.as_tensor(indptr), torch.as_tensor(indices)
+    return indptr.long().contiguous(), indices.to(indptr.device).long().contiguous()
+
+
+def _starts(n, walk_num, seed, device):
+    gen = torch.Generator().manual_seed(seed % (2 ** 63))
+    return torch.cat([torch.randperm(n, generator=gen) for _ in range(walk_num)]).to(device)
+
+
+def _embed(walk, graph_or_csr, dim, walk_length, walk_num, window, epochs, seed, negative, alpha, min_alpha, sample, workers):
+    walk_num = int(walk_num)
+    if walk_num < 1:
+        raise ValueError("walk_num must be >= 1 (got %d)" % walk_num)
+    indptr, indices = _csr(graph_or_csr)
+    n = indptr.numel() - 1
+    seed = _seed(seed)
+    start = _starts(n, walk_num, seed, indptr.device)
+    walks = walk(indptr, indices, start, (seed + 1) & (2 ** 64 - 1))
+    syn0, _ = skipgram(walks, n, dim=dim, window=window, negative=negative, epochs=epochs, alpha=alpha, min_alpha=min_alpha,
+                       sample=sample, seed=(seed + 2) & (2 ** 64 - 1), workers=workers)
+    return syn0
+
+
+def deepwalk(graph_or_csr, dim=128, walk_length=80, walk_num=40, window=5, epochs=5, seed=None, negative=5, alpha=0.025,
+             min_alpha=1e-4, sample=1e-3, workers=0):
+    """DeepWalk: uniform walks, then skip-gram with negative sampling.  -> float32 [N, dim] on the graph's device."""
+    return _embed(lambda ip, ix, st, sd: random_walk(ip, ix, st, walk_length, seed=sd), graph_or_csr, dim, walk_length, walk_num,
+                  window, epochs, seed, negative, alpha, min_alpha, sample, workers)
+
+
+def node2vec(graph_or_csr, dim=128, walk_length=80, walk_num=40, window=5, epochs=5, p=1.0, q=1.0, seed=None, negative=5,
+             alpha=0.025, min_alpha=1e-4, sample=1e-3, workers=0):
+    """node2vec: second-order walks with return parameter p and in-out parameter q, then skip-gram."""
+    return _embed(lambda ip, ix, st, sd: node2vec_walk(ip, ix, st, walk_length, p=p, q=q, seed=sd), graph_or_csr, dim, walk_length,
+                  walk_num, window, epochs, seed, negative, alpha, min_alpha, sample, workers)

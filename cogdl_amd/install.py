@@ -37,7 +37,7 @@ _finder = None
 
 
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
-            metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False):
+            metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -71,6 +71,13 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     matrix of pprgo and mvgrl comes from the library's PPR operator (HIP kernel when a GPU is visible, the OpenMP host twin
     otherwise).  Where cogdl.utils.ppr_utils cannot be imported (numba missing), cogdl_amd.ppr_compat is registered under
     that name, so the two models import at all.
+    skipgram=True registers cogdl_amd.gensim_compat as the module `gensim` (with gensim.models, gensim.models.word2vec and
+    gensim.models.keyedvectors) when the real package cannot be imported, so that the embedding models that train through
+    gensim.models.Word2Vec (deepwalk, node2vec, metapath2vec, dgk) import and train on the library's skip-gram operator, and
+    rebinds DeepWalk.forward and Node2vec.forward (opt-in: the draws are Philox's, not numpy's and gensim's generators, and
+    at a node without out-neighbours the walker stays instead of ending the walk) to versions that walk and train on the
+    graph's device through cogdl_amd.embedding, with the same return value (features_matrix as numpy [N, dim], or the dict
+    with return_dict=True).
     linear=True additionally routes torch.nn.functional.linear -- i.e. the unchanged nn.Linear inside every CogDL
     layer -- through cogdl_amd.linear (hand-written MFMA weight gradient for full-graph shapes)."""
     global _finder
@@ -136,6 +143,8 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
         _rebind_random_walker()
     if ppr:
         _rebind_ppr()
+    if skipgram:
+        _install_skipgram()
     su = sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):
@@ -241,7 +250,66 @@ def _rebind_ppr():
             setattr(mod, fn, getattr(ppr_compat, fn))
 
 
+_EMB_MODELS = (("cogdl.models.emb.deepwalk", "DeepWalk"), ("cogdl.models.emb.node2vec", "Node2vec"))
+
+
+def _embedding_matrix(model, graph, return_dict, emb):
+    import numpy as np
+
+    features_matrix = emb.detach().cpu().numpy().astype(np.float64)
+    if return_dict:
+        return dict((vid, features_matrix[vid]) for vid in range(graph.num_nodes))
+    return features_matrix
+
+
+def _deepwalk_forward(self, graph, embedding_model_creator=None, return_dict=False):
+    from . import embedding
+
+    emb = embedding.deepwalk(graph, dim=self.dimension, walk_length=self.walk_length, walk_num=self.walk_num,
+                             window=self.window_size, epochs=self.iteration)
+    return _embedding_matrix(self, graph, return_dict, emb)
+
+
+def _node2vec_forward(self, graph, return_dict=False):
+    from . import embedding
+
+    emb = embedding.node2vec(graph, dim=self.dimension, walk_length=self.walk_length, walk_num=self.walk_num,
+                             window=self.window_size, epochs=self.iteration, p=self.p, q=self.q)
+    return _embedding_matrix(self, graph, return_dict, emb)
+
+
+def _install_skipgram():
+    """gensim is served by cogdl_amd.gensim_compat where the real package is absent (the real one wins where it exists), then
+    the two models are imported and their forward rebound; the originals are kept for uninstall().  Without the cogdl
+    package only the module registration happens."""
+    from . import gensim_compat
+
+    if getattr(sys.modules.get("gensim"), "__name__", None) is None:  # not imported yet (or marked absent)
+        try:
+            sys.modules.pop("gensim", None)
+            importlib.import_module("gensim")
+        except Exception:
+            gensim_compat.register()
+    try:
+        importlib.import_module("cogdl")
+    except ImportError:
+        return
+    for (name, cls_name), fwd in zip(_EMB_MODELS, (_deepwalk_forward, _node2vec_forward)):
+        _import_target(name, "skipgram")
+        cls = getattr(sys.modules[name], cls_name)
+        if cls.forward is not fwd:
+            cls.__dict__.get("_cogdl_amd_orig_forward") or setattr(cls, "_cogdl_amd_orig_forward", cls.forward)
+            cls.forward = fwd
+
+
 def uninstall():
+    for name, cls_name in _EMB_MODELS:
+        cls = getattr(sys.modules.get(name), cls_name, None)
+        if cls is not None and "_cogdl_amd_orig_forward" in cls.__dict__:
+            cls.forward = cls.__dict__["_cogdl_amd_orig_forward"]
+            delattr(cls, "_cogdl_amd_orig_forward")
+    if "cogdl_amd.gensim_compat" in sys.modules:
+        sys.modules["cogdl_amd.gensim_compat"].unregister()
     for name in (_PPR_UTILS,) + _PPR_HOLDERS:
         mod = sys.modules.get(name)
         if mod is None:

@@ -9,6 +9,7 @@
 
     walk.py          random_walk, node2vec_walk (also exported here)   (cogdl/utils/sampling.py, models/emb/node2vec.py)
     ppr.py           topk_ppr, full_ppr (also exported here)           (cogdl/utils/ppr_utils.py)
+    sgns.py          skipgram (also exported here)                     (gensim's Word2Vec(sg=1) in models/emb/deepwalk.py)
 
     ops.py           scatter_add, op_aggr, s_*_e_sum / s_*_e_mean (fused HIP), s_*_e, s_*_t   (cogdl/operators/ops.py)
 
@@ -26,4 +27,8 @@ def __getattr__(name):
         from . import ppr
 
         return getattr(ppr, name)
+    if name == "skipgram":
+        from . import sgns
+
+        return sgns.skipgram
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

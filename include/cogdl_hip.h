@@ -805,6 +805,34 @@ COGDL_API int cogdl_hip_ppr_topk(const int64_t *indptr, const int64_t *indices, 
                        int64_t topk, int64_t *nbr, float *val, int32_t *count, int32_t *stats, int *flags, void *ws,
                        size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Skip-gram training with negative sampling (csrc/sgns.hip): the trainer behind gensim's Word2Vec(sg=1, negative=K) as
+ * cogdl/models/emb/deepwalk.py:54-80 and node2vec.py:72-103 call it, on walks that are already on the device.  The law --
+ * draws, order of updates, every rounding -- is csrc/sgns_law.h.  Host twin: cogdl_host_sgns_init / cogdl_host_sgns_train.
+ *   walks        int64 [W, L] row-major, ids in [0, V); a negative id is padding and is skipped.  L <= 1024.
+ *   D, window, negative   1..512, 1..32, 1..16.  epochs >= 1.  The learning rate falls linearly from alpha (first row of
+ *                the first epoch) towards min_alpha over epochs * W rows.
+ *   keep         uint32 [V]: a token is kept iff its draw <= keep[id] (2^32 - 1 keeps always).
+ *   cum          uint32 [V]: cumulative noise table, non-decreasing, last entry >= 1 (callers build 2^31 - 1).
+ *   exp_table    float [1000]: word2vec.c's sigmoid table, exp_table[i] = s / (s + 1), s = exp((2 i / 1000 - 1) * 6).
+ *   syn0, syn1   float [V, D] row-major, read and updated in place (cogdl_hip_sgns_init fills syn0 from the seed and
+ *                zeroes syn1; a caller may pass tables of its own to continue training).
+ *   workers      1: one launch of one wave, rows in order; the result equals the host twin's bit for bit.  Slow by
+ *                construction.  Anything else: launches of at most rows_in_flight rows (0 = the library's default) in row
+ *                order; the rows of one launch run concurrently and update the tables without locks, so results differ
+ *                from run to run.
+ *   *flags       device int, zeroed by the call, then set by a validation pass that runs before any update: bit 0 an id
+ *                >= V, bit 1 a cum that runs backwards or ends in 0.  Non-zero: the tables were not touched.  Nothing is
+ *                read out of bounds.
+ *   Stream-ordered, allocates nothing, does not synchronise.  Tuning key 17 selects the row update: 0 memory-side
+ *   atomicAdd(float) (default), 1 write-through read-modify-write stores.
+ * ------------------------------------------------------------------------------------------------------------------ */
+COGDL_API int cogdl_hip_sgns_init(float *syn0, float *syn1, int64_t V, int D, uint64_t seed, void *stream);
+COGDL_API int cogdl_hip_sgns_train(const int64_t *walks, int64_t W, int64_t L, int64_t V, int D, int window, int negative,
+                         int64_t epochs, double alpha, double min_alpha, const uint32_t *keep, const uint32_t *cum,
+                         const float *exp_table, uint64_t seed, int workers, int64_t rows_in_flight, float *syn0,
+                         float *syn1, int *flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,20 @@ COGDL_HOST_API int cogdl_host_ppr_topk(const int64_t *indptr, const int64_t *ind
                                        double eps, int64_t topk, int64_t *nbr, float *val, int32_t *count, int32_t *stats,
                                        int *flags);
 
+/* Skip-gram training with negative sampling; the host twin of cogdl_hip_sgns_init / cogdl_hip_sgns_train (include/cogdl_hip.h,
+ * where the contract is spelled out): same arguments minus rows_in_flight and the stream, all pointers host memory.
+ * workers == 1 is strictly sequential and returns EXACTLY the tables of the GPU's serial mode (both run csrc/sgns_law.h);
+ * workers == 0 (OpenMP's default thread count) or > 1 runs the rows of an epoch in parallel without locks.
+ * trace: NULL, or double [trace_cap, 6] filled in the sequential mode only (COGDL_HOST_EINVAL otherwise) with one record
+ * (epoch, row, input id, target id, label, learning rate) per applied target, in order; *trace_n receives the number of
+ * applied targets, which may exceed trace_cap (the surplus is not written). */
+COGDL_HOST_API int cogdl_host_sgns_init(float *syn0, float *syn1, int64_t V, int D, uint64_t seed);
+COGDL_HOST_API int cogdl_host_sgns_train(const int64_t *walks, int64_t W, int64_t L, int64_t V, int D, int window,
+                                         int negative, int64_t epochs, double alpha, double min_alpha, const uint32_t *keep,
+                                         const uint32_t *cum, const float *exp_table, uint64_t seed, int workers,
+                                         float *syn0, float *syn1, int *flags, double *trace, int64_t trace_cap,
+                                         int64_t *trace_n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,166 @@
+"""The skip-gram kernel (csrc/sgns.hip) on the GPU: the serial mode equals the host twin bit for bit over the replay grid of
+test_sgns_host.py; the throughput mode reaches the twin's embedding quality on the planted-partition graph; error flags
+instead of faults; stream use; walk-train-embed end to end, also through the reference's unchanged DeepWalk class."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from cogdl_amd import _lib, embedding
+from cogdl_amd.operators import skipgram
+from cogdl_amd.operators import sgns as sgns_mod
+
+from test_sgns_host import GRID, QUALITY, ROOT, corpus, grid_id, neighbour_purity, quality_instance, twin_purity
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+@pytest.mark.parametrize("case", GRID, ids=grid_id)
+def test_serial_mode_equals_the_host_twin_bit_for_bit(case):
+    w, l, d, v, sample = case
+    walks = corpus(w, l, v)
+    kw = dict(dim=d, window=3, negative=4, epochs=2, alpha=0.05, sample=sample, seed=11, workers=1)
+    host = skipgram(walks, v, **kw)
+    gpu = skipgram(walks.to(DEV), v, **kw)
+    assert gpu[0].is_cuda and gpu[0].dtype == torch.float32 and tuple(gpu[0].shape) == (v, d)
+    assert torch.equal(host[0], gpu[0].cpu()), "syn0: max difference %g" % float((host[0] - gpu[0].cpu()).abs().max())
+    assert torch.equal(host[1], gpu[1].cpu()), "syn1: max difference %g" % float((host[1] - gpu[1].cpu()).abs().max())
+
+
+def test_serial_mode_continues_from_the_callers_tables_and_runs_twice_alike():
+    walks = corpus(64, 40, 500)
+    kw = dict(dim=65, window=5, negative=5, epochs=1, seed=3, workers=1)
+    first = skipgram(walks, 500, **kw)
+    host = skipgram(walks, 500, init=first, **dict(kw, seed=4))
+    init = (first[0].to(DEV), first[1].to(DEV))
+    gpu = skipgram(walks.to(DEV), 500, init=init, **dict(kw, seed=4))
+    again = skipgram(walks.to(DEV), 500, init=init, **dict(kw, seed=4))
+    assert torch.equal(init[0].cpu(), first[0]) and torch.equal(init[1].cpu(), first[1])  # init is not modified
+    assert torch.equal(host[0], gpu[0].cpu()) and torch.equal(host[1], gpu[1].cpu())
+    assert torch.equal(gpu[0], again[0]) and torch.equal(gpu[1], again[1])
+
+
+def test_throughput_mode_reaches_the_twins_quality_on_the_planted_partition():
+    _, _, n, community, walks = quality_instance()
+    host = twin_purity()
+    init = sgns_mod.init_tables(n, QUALITY["dim"], 2, DEV)
+    syn0, syn1 = skipgram(walks.to(DEV), n, seed=2, init=init, **QUALITY)
+    got = neighbour_purity(syn0, community)
+    print("neighbour purity: GPU throughput mode %.4f, sequential host twin %.4f" % (got, host))
+    assert torch.isfinite(syn0).all() and torch.isfinite(syn1).all()
+    assert not torch.equal(syn0, init[0]) and not torch.equal(syn1, init[1])
+    assert got >= host - 0.05
+
+
+def test_throughput_mode_with_few_rows_in_flight(monkeypatch):
+    """Launches of 8 rows: a chunk that is no multiple of the workgroup's rows at the end (W = 61), D over 64."""
+    walks = corpus(61, 40, 500)
+    monkeypatch.setattr(sgns_mod, "ROWS_IN_FLIGHT", 8)
+    init = sgns_mod.init_tables(500, 200, 5, DEV)
+    syn0, syn1 = skipgram(walks.to(DEV), 500, dim=200, epochs=2, seed=5, init=init, sample=0.0)
+    ref = skipgram(walks, 500, dim=200, epochs=2, seed=5, workers=1, sample=0.0)
+    assert torch.isfinite(syn0).all() and not torch.equal(syn0, init[0])
+    # Hogwild over rows of a 500-id corpus: close to the sequential result, not equal to it
+    assert float((syn0.cpu() - ref[0]).abs().max()) < 0.05 * float(ref[0].abs().max())
+
+
+def test_flags_instead_of_faults():
+    walks = corpus(64, 40, 500)
+    bad = walks.clone()
+    bad[5, 7] = 500
+    with pytest.raises(_lib.BackendError, match="outside"):
+        skipgram(bad.to(DEV), 500, dim=16, seed=1)
+    bad[5, 7] = 2 ** 40
+    with pytest.raises(_lib.BackendError, match="outside"):
+        skipgram(bad.to(DEV), 500, dim=16, seed=1, workers=1)
+    keep = torch.full((500,), 2 ** 32 - 1)
+    cum = torch.linspace(1, 2 ** 31 - 1, 500).long()
+    cum[100] = cum[99] - 1
+    with pytest.raises(_lib.BackendError, match="noise table"):
+        skipgram(walks.to(DEV), 500, dim=16, seed=1, tables=(keep, cum))
+    with pytest.raises(_lib.BackendError, match="noise table"):
+        skipgram(walks.to(DEV), 500, dim=16, seed=1, tables=(keep, torch.zeros(500, dtype=torch.long)))
+    # the tables are not touched when a flag is raised
+    lib = _lib.hip()
+    init = sgns_mod.init_tables(500, 16, 1, DEV)
+    syn0, syn1 = init[0].clone(), init[1].clone()
+    flags = torch.zeros(1, dtype=torch.int32, device=DEV)
+    k32, c32, table, wd = sgns_mod._u32(keep, DEV), sgns_mod._u32(cum, DEV), sgns_mod.exp_table().to(DEV), walks.to(DEV)
+    rc = lib.cogdl_hip_sgns_train(_lib.ptr(wd), 64, 40, 500, 16, 5, 5, 1, 0.025, 1e-4, _lib.ptr(k32), _lib.ptr(c32), _lib.ptr(table), 1,
+                                  0, 0, _lib.ptr(syn0), _lib.ptr(syn1), _lib.ptr(flags), _lib.stream_of(wd))
+    assert rc == 0 and int(flags) == 2
+    assert torch.equal(syn0, init[0]) and torch.equal(syn1, init[1])
+    torch.cuda.synchronize()
+    good = skipgram(walks.to(DEV), 500, dim=16, seed=1)  # the device is fine afterwards
+    assert torch.isfinite(good[0]).all()
+
+
+def test_skipgram_on_a_side_stream_is_ordered_with_the_callers_work():
+    walks = corpus(64, 40, 500)
+    want = skipgram(walks, 500, dim=64, epochs=1, seed=8, workers=1)
+    side = torch.cuda.Stream(device=DEV)
+    with torch.cuda.stream(side):
+        big = torch.randn(4096, 4096, device=DEV)
+        for _ in range(4):
+            big = big @ big * 1e-3  # work in front of the call on this stream
+        wd = torch.zeros((64, 40), dtype=torch.long, device=DEV)
+        wd.copy_(walks.to(DEV), non_blocking=True)  # the kernel must see this copy
+        syn0, syn1 = skipgram(wd, 500, dim=64, epochs=1, seed=8, workers=1)
+        total = syn0.sum() + syn1.sum()  # and this must see the kernel's result
+    side.synchronize()
+    assert torch.equal(syn0.cpu(), want[0]) and torch.equal(syn1.cpu(), want[1])
+    assert float(total) == pytest.approx(float(want[0].sum() + want[1].sum()), rel=1e-4, abs=1e-5)
+
+
+# ------------------------------------------------------------------------------------------------------- end to end
+def test_deepwalk_and_node2vec_embed_the_planted_partition():
+    indptr, indices, n, community, _ = quality_instance()
+    csr = (indptr.to(DEV), indices.to(DEV))
+    emb = embedding.deepwalk(csr, dim=32, walk_length=40, walk_num=10, window=5, epochs=5, seed=1)
+    assert emb.is_cuda and tuple(emb.shape) == (n, 32)
+    got = neighbour_purity(emb, community)
+    emb2 = embedding.node2vec(csr, dim=32, walk_length=40, walk_num=10, window=5, epochs=5, p=0.5, q=2.0, seed=1)
+    got2 = neighbour_purity(emb2, community)
+    print("neighbour purity: deepwalk %.4f, node2vec %.4f" % (got, got2))
+    assert got >= 0.9 and got2 >= 0.9
+
+
+REF_PKG = os.path.join(ROOT, "oracle", "_ref", "pkg")
+
+REFERENCE_SCRIPT = r'''
+import sys
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
+import numpy as np, torch
+from tools import refpkg
+refpkg.setup(install=True)
+from cogdl_amd.install import install, uninstall
+install(skipgram=True)
+from cogdl.data import Graph
+from cogdl.models.emb.deepwalk import DeepWalk
+from test_sgns_host import planted_partition, neighbour_purity
+indptr, indices, n, community = planted_partition()
+row = torch.repeat_interleave(torch.arange(n), indptr[1:] - indptr[:-1])
+g = Graph(edge_index=torch.stack([row, indices]), num_nodes=n).to(sys.argv[2])
+model = DeepWalk(32, 40, 10, 5, 4, 5)
+torch.manual_seed(1)
+emb = model(g)
+assert isinstance(emb, np.ndarray) and emb.shape == (n, 32), emb.shape
+d = model.forward(g, return_dict=True)
+assert isinstance(d, dict) and len(d) == n and d[5].shape == (32,)
+print("purity %.4f" % neighbour_purity(torch.from_numpy(emb), community))
+uninstall()
+assert DeepWalk.forward.__module__ == "cogdl.models.emb.deepwalk"
+'''
+
+
+@pytest.mark.skipif(not os.path.isdir(os.path.join(REF_PKG, "cogdl")), reason="the reference package is not staged under oracle/_ref/pkg")
+def test_reference_deepwalk_class_runs_under_install_skipgram():
+    out = subprocess.run([sys.executable, "-c", REFERENCE_SCRIPT, ROOT, DEV], capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-3000:]
+    purity = float(out.stdout.strip().splitlines()[-1].split()[-1])
+    print("reference DeepWalk under install(skipgram=True): neighbour purity %.4f" % purity)
+    assert purity >= 0.9
