@@ -12,12 +12,12 @@ import sys
 
 import torch
 
+from . import _rebind
 from .operators.spmm import csrspmm
 from .plan import tensor_key
 
 BIG_EDGES = 2 ** 31 - 2 ** 20  # COGDL_HIP_SEGMENT_MAX_EDGES: what one 32-bit launch takes (tests lower it)
 _ATTR = "__cogdl_amd_big_colind32__"
-_orig = {}
 
 
 def _colind32(graph):
@@ -84,17 +84,9 @@ def install():
     if getattr(su.spmm, "_cogdl_amd_big", False):
         return True
     reference_spmm = su.spmm
-    front = make_spmm(reference_spmm)
-    for name, mod in list(sys.modules.items()):
-        if name.startswith("cogdl") and mod is not None and getattr(mod, "spmm", None) is reference_spmm:
-            _orig[name] = reference_spmm
-            mod.spmm = front
+    _rebind.put_where_held("big_graphs", "spmm", make_spmm(reference_spmm), lambda cur: cur is reference_spmm)
     return True
 
 
 def uninstall():
-    for name, fn in _orig.items():
-        mod = sys.modules.get(name)
-        if mod is not None and getattr(getattr(mod, "spmm", None), "_cogdl_amd_big", False):
-            mod.spmm = fn
-    _orig.clear()
+    _rebind.undo("big_graphs")

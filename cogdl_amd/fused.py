@@ -12,11 +12,9 @@ import sys
 
 import torch
 
-from . import _lib
+from . import _lib, _rebind
 from . import linear as _linear
 from .operators.spmm import csrspmm_fused
-
-_orig = {}  # module name -> the reference's spmm
 
 
 def make_spmm(reference_spmm):
@@ -49,20 +47,13 @@ def install():
     if getattr(su.spmm, "_cogdl_amd_fused", False):
         return True
     reference_spmm = su.spmm
-    fused = make_spmm(reference_spmm)
-    for name, mod in list(sys.modules.items()):
-        if name.startswith("cogdl") and mod is not None and getattr(mod, "spmm", None) is reference_spmm:
-            _orig[name] = reference_spmm
-            mod.spmm = fused
+    _rebind.put_where_held("fused_norm", "spmm", make_spmm(reference_spmm), lambda cur: cur is reference_spmm)
     return True
 
 
 def uninstall():
-    for name, fn in _orig.items():
-        mod = sys.modules.get(name)
-        if mod is not None:
-            mod.spmm = fn
-    _orig.clear()
+    """All three of this module's features (and whatever was stacked on the fused `spmm` front afterwards)."""
+    _rebind.undo("fused_norm")
     uninstall_narrow_side()
     uninstall_gat_dropout()
 
@@ -76,7 +67,6 @@ def uninstall():
 # -- the aggregation at the input width, one extra SpMM of width 1 for the row sums of A (the graph's weights may change
 # between calls, so they are not cached).  Same operator, same dispatcher, same parameters; fp32 results differ by
 # reassociation only (checked to 1e-5 against the reference's order, tests/test_install_reference.py).
-_orig_gcn_forward = {}
 
 
 def _gcn_forward_narrow_side(self, graph, x):
@@ -105,17 +95,12 @@ def install_narrow_side():
     mod = sys.modules.get("cogdl.layers.gcn_layer")
     if mod is None:
         return False
-    cls = mod.GCNLayer
-    if cls.forward is not _gcn_forward_narrow_side:
-        _orig_gcn_forward[cls] = cls.forward
-        cls.forward = _gcn_forward_narrow_side
+    _rebind.put("narrow_side", mod.GCNLayer, "forward", _gcn_forward_narrow_side)
     return True
 
 
 def uninstall_narrow_side():
-    for cls, fn in _orig_gcn_forward.items():
-        cls.forward = fn
-    _orig_gcn_forward.clear()
+    _rebind.undo("narrow_side")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -129,7 +114,6 @@ def uninstall_narrow_side():
 # parameters, same statistics of the mask (each attention element kept with probability 1 - p and scaled by 1/(1 - p),
 # independently), a different random stream than torch's; with attn_drop = 0 or in eval mode it is the reference's own
 # fused branch without the `graph.is_symmetric()` restriction (the operator uses the true transpose).
-_orig_gat_forward = {}
 
 
 def _column_sum(t, block=512):
@@ -199,7 +183,7 @@ class _HeadProjections(torch.autograd.Function):
 
 def _gat_forward_fused_dropout(self, graph, x):
     if not (torch.is_tensor(x) and x.is_cuda):
-        return _orig_gat_forward[type(self)](self, graph, x)
+        return _rebind.original(type(self), "forward")(self, graph, x)
     from .operators.fused_gat import fused_gat_dropout_func
 
     # (bf16 autocast, tall x: the hand-written MFMA product that reads x once, cogdl_amd/linear.py: matmul; else torch.matmul)
@@ -225,14 +209,9 @@ def install_gat_dropout():
     mod = sys.modules.get("cogdl.layers.gat_layer")
     if mod is None:
         return False
-    cls = mod.GATLayer
-    if cls.forward is not _gat_forward_fused_dropout:
-        _orig_gat_forward[cls] = cls.forward
-        cls.forward = _gat_forward_fused_dropout
+    _rebind.put("fused_gat_dropout", mod.GATLayer, "forward", _gat_forward_fused_dropout)
     return True
 
 
 def uninstall_gat_dropout():
-    for cls, fn in _orig_gat_forward.items():
-        cls.forward = fn
-    _orig_gat_forward.clear()
+    _rebind.undo("fused_gat_dropout")

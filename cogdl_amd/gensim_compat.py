@@ -17,6 +17,7 @@ import types
 import numpy as np
 import torch
 
+from . import _rebind
 from .operators import sgns as _sgns
 
 
@@ -107,13 +108,9 @@ SUBMODULES = {"gensim.models": models, "gensim.models.word2vec": models.word2vec
 
 def register():
     """Serve this module as `gensim` (install(skipgram=True) calls it only when the real package is absent)."""
-    sys.modules["gensim"] = sys.modules[__name__]
-    sys.modules.update(SUBMODULES)
+    for name, mod in [("gensim", sys.modules[__name__])] + list(SUBMODULES.items()):
+        _rebind.put("gensim", sys.modules, name, mod)
 
 
 def unregister():
-    if sys.modules.get("gensim") is sys.modules[__name__]:
-        del sys.modules["gensim"]
-    for name, mod in SUBMODULES.items():
-        if sys.modules.get(name) is mod:
-            del sys.modules[name]
+    _rebind.undo("gensim")

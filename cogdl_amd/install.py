@@ -16,6 +16,8 @@ import importlib.abc
 import importlib.util
 import sys
 
+from . import _rebind
+
 REPLACED = ("spmm", "edge_softmax", "mhspmm", "scatter_max", "fused_gat", "sample", "ops")
 _PREFIX = "cogdl.operators."
 
@@ -88,16 +90,14 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
         name = _PREFIX + op
         if name in sys.modules and not getattr(sys.modules[name], "__name__", "").startswith("cogdl_amd."):
             mod = importlib.import_module("cogdl_amd.operators." + op)
-            sys.modules[name] = mod
+            _rebind.put("operators", sys.modules, name, mod)
             pkg = sys.modules.get("cogdl.operators")
             if pkg is not None:
-                setattr(pkg, op, mod)
+                _rebind.put("operators", pkg, op, mod)
                 if op == "ops":  # cogdl/operators/__init__.py:1-16 re-exports the s_* names from .ops
-                    saved = pkg.__dict__.setdefault("_cogdl_amd_orig_ops", {})
                     for attr in dir(mod):
                         if attr.startswith("s_") and hasattr(pkg, attr):
-                            saved.setdefault(attr, getattr(pkg, attr))
-                            setattr(pkg, attr, getattr(mod, attr))
+                            _rebind.put("operators", pkg, attr, getattr(mod, attr))
     _rebind_graph_build()
     if linear:
         from . import linear as _linear
@@ -129,16 +129,10 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
         _import_target("cogdl.data.data", "structure_memo")
         if not _memo.install():
             raise _lib_error("install(structure_memo=True): Graph.row_indptr / col_indices could not be rebound")
-    if metis and "metis" not in sys.modules:
-        try:
-            importlib.import_module("metis")  # the real one wins where it exists
-        except Exception:  # (ImportError, or the wrapper's RuntimeError when libmetis is missing)
-            sys.modules["metis"] = importlib.import_module("cogdl_amd.metis_compat")
-    if torch_sparse and "torch_sparse" not in sys.modules:
-        try:
-            importlib.import_module("torch_sparse")  # the real one wins where it exists
-        except Exception:
-            sys.modules["torch_sparse"] = importlib.import_module("cogdl_amd.torch_sparse_compat")
+    if metis:
+        _serve_where_absent("metis")
+    if torch_sparse:
+        _serve_where_absent("torch_sparse")
     if random_walk:
         _rebind_random_walker()
     if ppr:
@@ -159,6 +153,17 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     return [_PREFIX + op for op in REPLACED]
 
 
+def uninstall():
+    """Revert every recorded rebind, newest first (cogdl_amd/_rebind.py), then drop the finder and what it served."""
+    _rebind.undo()
+    global _finder
+    if _finder is not None:
+        sys.meta_path.remove(_finder)
+        _finder = None
+    for op in REPLACED:
+        mod = sys.modules.get(_PREFIX + op)
+        if mod is not None and getattr(mod, "__name__", "").startswith("cogdl_amd."):
+            del sys.modules[_PREFIX + op]
 
 
 def _lib_error(msg):
@@ -176,6 +181,15 @@ def _import_target(name, flag):
         raise _lib_error("install(%s=True) needs the cogdl package (importing %s failed: %s)" % (flag, name, e)) from e
 
 
+def _serve_where_absent(name):
+    """Register cogdl_amd.<name>_compat as the module `name` unless that name is taken or the real package imports."""
+    if name not in sys.modules:
+        try:
+            importlib.import_module(name)  # the real one wins where it exists
+        except Exception:  # (ImportError, or the metis wrapper's RuntimeError when libmetis is missing)
+            _rebind.put(name, sys.modules, name, importlib.import_module("cogdl_amd.%s_compat" % name))
+
+
 _GRAPH_BUILD_NAMES = ("coo2csr_index", "add_remaining_self_loops", "symmetric_normalization", "row_normalization")
 
 
@@ -186,18 +200,9 @@ def _rebind_graph_build():
     again after `import cogdl` if it ran before (install() is idempotent)."""
     from . import graph_build
 
-    for name, mod in list(sys.modules.items()):
-        if mod is None or not (name == "cogdl" or name.startswith("cogdl.")):
-            continue
-        for fn in _GRAPH_BUILD_NAMES:
-            cur = getattr(mod, fn, None)
-            if cur is None or getattr(cur, "__module__", "") == "cogdl_amd.graph_build":
-                continue
-            if getattr(cur, "__module__", "") != "cogdl.utils.graph_utils":
-                continue
-            saved = mod.__dict__.setdefault("_cogdl_amd_orig_graph_build", {})
-            saved.setdefault(fn, cur)
-            setattr(mod, fn, getattr(graph_build, fn))
+    for fn in _GRAPH_BUILD_NAMES:
+        _rebind.put_where_held("graph_build", fn, getattr(graph_build, fn),
+                               lambda cur: getattr(cur, "__module__", "") == "cogdl.utils.graph_utils")
 
 
 _RANDOM_WALKER_MODULES = ("cogdl.utils.sampling", "cogdl.utils", "cogdl.data.data", "cogdl.data.sampler")
@@ -205,18 +210,14 @@ _RANDOM_WALKER_MODULES = ("cogdl.utils.sampling", "cogdl.utils", "cogdl.data.dat
 
 def _rebind_random_walker():
     """The four modules that hold the reference's RandomWalker by name (`from cogdl.utils import RandomWalker` copies it) are
-    imported if need be and rebound; the originals are kept for uninstall()."""
+    imported if need be and rebound."""
     from .random_walk_compat import RandomWalker
 
     for name in _RANDOM_WALKER_MODULES:
         _import_target(name, "random_walk")
-        mod = sys.modules[name]
-        cur = getattr(mod, "RandomWalker", None)
-        if cur is None:
+        if getattr(sys.modules[name], "RandomWalker", None) is None:
             raise _lib_error("install(random_walk=True): %s has no RandomWalker to rebind" % name)
-        if cur is not RandomWalker:
-            mod.__dict__.setdefault("_cogdl_amd_orig_random_walker", cur)
-            mod.RandomWalker = RandomWalker
+        _rebind.put("random_walk", sys.modules[name], "RandomWalker", RandomWalker)
 
 
 _PPR_NAMES = ("ppr_topk", "topk_ppr_matrix", "build_topk_ppr_matrix_from_data")
@@ -226,16 +227,15 @@ _PPR_HOLDERS = ("cogdl.wrappers.data_wrapper.node_classification.pprgo_dw", "cog
 
 def _rebind_ppr():
     """cogdl.utils.ppr_utils is imported (or, where numba is missing, served by cogdl_amd.ppr_compat under that name), then
-    the three functions are rebound there and in the two modules that copied one by name; the originals are kept for
-    uninstall()."""
+    the three functions are rebound there and in the two modules that copied one by name."""
     from . import ppr_compat
 
     _import_target("cogdl.utils", "ppr")
     try:
         importlib.import_module(_PPR_UTILS)
     except ImportError:  # numba missing: the reference module cannot load
-        sys.modules[_PPR_UTILS] = ppr_compat
-        sys.modules["cogdl.utils"].ppr_utils = ppr_compat
+        _rebind.put("ppr", sys.modules, _PPR_UTILS, ppr_compat)
+        _rebind.put("ppr", sys.modules["cogdl.utils"], "ppr_utils", ppr_compat)
     for name in _PPR_HOLDERS:  # (before anything is rebound: they copy the names they will get back at uninstall())
         _import_target(name, "ppr")
     for name in (_PPR_UTILS,) + _PPR_HOLDERS:
@@ -243,11 +243,8 @@ def _rebind_ppr():
         if mod is ppr_compat:
             continue
         for fn in _PPR_NAMES:
-            cur = getattr(mod, fn, None)
-            if cur is None or cur is getattr(ppr_compat, fn):
-                continue
-            mod.__dict__.setdefault("_cogdl_amd_orig_ppr", {}).setdefault(fn, cur)
-            setattr(mod, fn, getattr(ppr_compat, fn))
+            if getattr(mod, fn, None) is not None:
+                _rebind.put("ppr", mod, fn, getattr(ppr_compat, fn))
 
 
 _EMB_MODELS = (("cogdl.models.emb.deepwalk", "DeepWalk"), ("cogdl.models.emb.node2vec", "Node2vec"))
@@ -280,8 +277,8 @@ def _node2vec_forward(self, graph, return_dict=False):
 
 def _install_skipgram():
     """gensim is served by cogdl_amd.gensim_compat where the real package is absent (the real one wins where it exists), then
-    the two models are imported and their forward rebound; the originals are kept for uninstall().  Without the cogdl
-    package only the module registration happens."""
+    the two models are imported and their forward rebound.  Without the cogdl package only the module registration
+    happens."""
     from . import gensim_compat
 
     if getattr(sys.modules.get("gensim"), "__name__", None) is None:  # not imported yet (or marked absent)
@@ -296,59 +293,5 @@ def _install_skipgram():
         return
     for (name, cls_name), fwd in zip(_EMB_MODELS, (_deepwalk_forward, _node2vec_forward)):
         _import_target(name, "skipgram")
-        cls = getattr(sys.modules[name], cls_name)
-        if cls.forward is not fwd:
-            cls.__dict__.get("_cogdl_amd_orig_forward") or setattr(cls, "_cogdl_amd_orig_forward", cls.forward)
-            cls.forward = fwd
+        _rebind.put("skipgram", getattr(sys.modules[name], cls_name), "forward", fwd)
 
-
-def uninstall():
-    for name, cls_name in _EMB_MODELS:
-        cls = getattr(sys.modules.get(name), cls_name, None)
-        if cls is not None and "_cogdl_amd_orig_forward" in cls.__dict__:
-            cls.forward = cls.__dict__["_cogdl_amd_orig_forward"]
-            delattr(cls, "_cogdl_amd_orig_forward")
-    if "cogdl_amd.gensim_compat" in sys.modules:
-        sys.modules["cogdl_amd.gensim_compat"].unregister()
-    for name in (_PPR_UTILS,) + _PPR_HOLDERS:
-        mod = sys.modules.get(name)
-        if mod is None:
-            continue
-        if getattr(mod, "__name__", "") == "cogdl_amd.ppr_compat":  # registered in place of the module that cannot load
-            del sys.modules[name]
-            utils = sys.modules.get("cogdl.utils")
-            if utils is not None and getattr(utils, "ppr_utils", None) is mod:
-                del utils.ppr_utils
-            continue
-        for fn, orig in mod.__dict__.pop("_cogdl_amd_orig_ppr", {}).items():
-            setattr(mod, fn, orig)
-    for name in _RANDOM_WALKER_MODULES:
-        mod = sys.modules.get(name)
-        if mod is not None and "_cogdl_amd_orig_random_walker" in mod.__dict__:
-            mod.RandomWalker = mod.__dict__.pop("_cogdl_amd_orig_random_walker")
-    if getattr(sys.modules.get("torch_sparse"), "__name__", "") == "cogdl_amd.torch_sparse_compat":
-        del sys.modules["torch_sparse"]
-    if "cogdl_amd.big_dispatch" in sys.modules:
-        sys.modules["cogdl_amd.big_dispatch"].uninstall()
-    if "cogdl_amd.structure_memo" in sys.modules:
-        sys.modules["cogdl_amd.structure_memo"].uninstall()
-    if "cogdl_amd.linear" in sys.modules:
-        sys.modules["cogdl_amd.linear"].uninstall()
-    if "cogdl_amd.fused" in sys.modules:
-        sys.modules["cogdl_amd.fused"].uninstall()
-    for name, mod in list(sys.modules.items()):
-        if mod is not None and (name == "cogdl" or name.startswith("cogdl.")):
-            for fn, orig in mod.__dict__.pop("_cogdl_amd_orig_graph_build", {}).items():
-                setattr(mod, fn, orig)
-    pkg = sys.modules.get("cogdl.operators")
-    if pkg is not None:
-        for attr, orig in pkg.__dict__.pop("_cogdl_amd_orig_ops", {}).items():
-            setattr(pkg, attr, orig)
-    global _finder
-    if _finder is not None:
-        sys.meta_path.remove(_finder)
-        _finder = None
-    for op in REPLACED:
-        mod = sys.modules.get(_PREFIX + op)
-        if mod is not None and getattr(mod, "__name__", "").startswith("cogdl_amd."):
-            del sys.modules[_PREFIX + op]

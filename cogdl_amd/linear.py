@@ -16,7 +16,7 @@ where that kernel is the faster one (<= 64 output columns, weight <= 96 KB), els
 """
 import torch
 
-from . import _lib
+from . import _lib, _rebind
 
 MIN_ROWS = 4096      # below this the reduction is too short to matter
 MAX_FEATURES = 4096  # in/out features covered by the kernel's tiling
@@ -248,8 +248,8 @@ def linear(x, weight, bias=None):
 def install():
     """Idempotent: torch.nn.functional.linear (what nn.Linear.forward calls) -> `linear` above."""
     _lib.hip()  # fail loudly if the library is missing
-    torch.nn.functional.linear = linear
+    _rebind.put("linear", torch.nn.functional, "linear", linear)
 
 
 def uninstall():
-    torch.nn.functional.linear = _orig_linear
+    _rebind.undo("linear")

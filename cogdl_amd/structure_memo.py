@@ -20,10 +20,10 @@ import sys
 
 import torch
 
+from . import _rebind
 from .plan import Fingerprint
 
 _ATTR = "__cogdl_amd_structure_memo__"  # (double underscores on both sides: outside Adjacency.keys, data.py:352-356)
-_orig = {}
 
 
 class StructureMemo:
@@ -100,16 +100,15 @@ def install():
     if mod is None:
         return False
     cls = mod.Graph
-    if cls in _orig:
+    if _rebind.original(cls, "row_indptr") is not None:
         return True
     p_row, p_col = cls.__dict__["row_indptr"], cls.__dict__["col_indices"]
-    _orig[cls] = (p_row, p_col)
-    cls.row_indptr = property(lambda self: _wrap(self._adj, p_row.fget(self), 0), p_row.fset, p_row.fdel, p_row.__doc__)
-    cls.col_indices = property(lambda self: _wrap(self._adj, p_col.fget(self), 1), p_col.fset, p_col.fdel, p_col.__doc__)
+    _rebind.put("structure_memo", cls, "row_indptr",
+                property(lambda self: _wrap(self._adj, p_row.fget(self), 0), p_row.fset, p_row.fdel, p_row.__doc__))
+    _rebind.put("structure_memo", cls, "col_indices",
+                property(lambda self: _wrap(self._adj, p_col.fget(self), 1), p_col.fset, p_col.fdel, p_col.__doc__))
     return True
 
 
 def uninstall():
-    for cls, (p_row, p_col) in _orig.items():
-        cls.row_indptr, cls.col_indices = p_row, p_col
-    _orig.clear()
+    _rebind.undo("structure_memo")

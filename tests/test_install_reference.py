@@ -116,7 +116,8 @@ import cogdl.utils.graph_utils as gu
 for fn in ("add_remaining_self_loops", "symmetric_normalization", "row_normalization", "coo2csr_index"):
     assert getattr(gu, fn).__module__ == "cogdl_amd.graph_build", fn
 assert cogdl.utils.row_normalization.__module__ == "cogdl_amd.graph_build"
-orig = gu._cogdl_amd_orig_graph_build
+from cogdl_amd._rebind import original
+orig = {fn: original(gu, fn) for fn in ("add_remaining_self_loops", "symmetric_normalization", "row_normalization")}
 r0, c0 = torch.randint(0, 50, (2, 400))
 w0 = torch.rand(400)
 (ra, ca), wa = gu.add_remaining_self_loops((r0, c0), w0, 1, 50)
