@@ -135,6 +135,15 @@ HIP_SIGNATURES = {
     "cogdl_hip_sgns_init": ([_vp, _vp, _i64, _i32, _u64, _vp], _i32),
     "cogdl_hip_sgns_train": ([_vp, _i64, _i64, _i64, _i32, _i32, _i32, _i64, _f64, _f64, _vp, _vp, _vp, _u64, _i32, _i64,
                               _vp, _vp, _vp, _vp], _i32),
+    # batched graph readout (csrc/readout.hip)
+    "cogdl_hip_segment_exact_nodes": ([], _i32),
+    "cogdl_hip_sort_pool_lds_nodes": ([], _i32),
+    "cogdl_hip_segment_ptr": ([_vp, _i64, _i64, _vp, _vp, _vp], _i32),
+    "cogdl_hip_segment_pool_fwd": ([_vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp], _i32),
+    "cogdl_hip_segment_pool_bwd": ([_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp], _i32),
+    "cogdl_hip_sort_pool_workspace_bytes": ([_i64], _sz),
+    "cogdl_hip_sort_pool_fwd": ([_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _sz, _vp], _i32),
+    "cogdl_hip_sort_pool_bwd": ([_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp], _i32),
 }
 
 MAX_SEGMENTS = 64  # COGDL_HIP_MAX_SEGMENTS
@@ -161,6 +170,12 @@ HOST_SIGNATURES = {
     "cogdl_host_sgns_init": ([_vp, _vp, _i64, _i32, _u64], _i32),
     "cogdl_host_sgns_train": ([_vp, _i64, _i64, _i64, _i32, _i32, _i32, _i64, _f64, _f64, _vp, _vp, _vp, _u64, _i32,
                                _vp, _vp, _vp, _vp, _i64, _vp], _i32),
+    "cogdl_host_segment_exact_nodes": ([], _i32),
+    "cogdl_host_segment_ptr": ([_vp, _i64, _i64, _vp, _vp], _i32),
+    "cogdl_host_segment_pool_fwd": ([_vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp], _i32),
+    "cogdl_host_segment_pool_bwd": ([_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp], _i32),
+    "cogdl_host_sort_pool_fwd": ([_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp], _i32),
+    "cogdl_host_sort_pool_bwd": ([_vp, _vp, _i64, _i64, _i64, _i64, _vp], _i32),
 }
 
 EUNSUPPORTED = 7  # COGDL_HIP_EUNSUPPORTED

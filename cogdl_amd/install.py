@@ -39,7 +39,7 @@ _finder = None
 
 
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
-            metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False):
+            metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False, readout=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -80,6 +80,14 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     at a node without out-neighbours the walker stays instead of ending the walk) to versions that walk and train on the
     graph's device through cogdl_amd.embedding, with the same return value (features_matrix as numpy [N, dim], or the dict
     with return_dict=True).
+    readout=True rebinds `batch_sum_pooling`, `batch_mean_pooling` and `batch_max_pooling` in cogdl.utils.utils and the by-name
+    copies in cogdl.utils, cogdl.models.nn.gcc_model, cogdl.models.nn.infograph, cogdl.layers.deepergcn_layer and
+    cogdl.layers.set2set, and rebinds GIN.forward and SortPool.forward (opt-in: no longer the unchanged models) to
+    cogdl_amd.readout_compat: the graph readout runs on the library's segment reduction and top-k operators (HIP kernels for
+    CUDA tensors, the OpenMP host twin otherwise) instead of zeros + scatter_add_, a CSR built per call, or SortPool's dense
+    pad + sort + gather.  No float atomics: sums are equal from run to run, and equal to the reference's CPU sums bit for bit;
+    max pooling also runs on the CPU without torch_scatter; equal SortPool keys go in row order.  A batch vector that is
+    unsorted or empty, an x that is not 2-D float32, and a mean over absent graph ids go to the reference's own functions.
     linear=True additionally routes torch.nn.functional.linear -- i.e. the unchanged nn.Linear inside every CogDL
     layer -- through cogdl_amd.linear (hand-written MFMA weight gradient for full-graph shapes)."""
     global _finder
@@ -139,6 +147,8 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
         _rebind_ppr()
     if skipgram:
         _install_skipgram()
+    if readout:
+        _rebind_readout()
     su = sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):
@@ -245,6 +255,27 @@ def _rebind_ppr():
         for fn in _PPR_NAMES:
             if getattr(mod, fn, None) is not None:
                 _rebind.put("ppr", mod, fn, getattr(ppr_compat, fn))
+
+
+_READOUT_NAMES = ("batch_sum_pooling", "batch_mean_pooling", "batch_max_pooling")
+_READOUT_HOLDERS = ("cogdl.utils.utils", "cogdl.utils", "cogdl.models.nn.gcc_model", "cogdl.models.nn.infograph",
+                    "cogdl.layers.deepergcn_layer", "cogdl.layers.set2set")
+_READOUT_MODELS = (("cogdl.models.nn.gin", "GIN", "gin_forward"), ("cogdl.models.nn.sortpool", "SortPool", "sortpool_forward"))
+
+
+def _rebind_readout():
+    """The modules that hold a pooling function by name and the two models are imported (before anything is rebound: they
+    copy the names they will get back at uninstall()), then every holder of a reference pooling function and the two forward
+    methods are rebound."""
+    from . import readout_compat
+
+    for name in _READOUT_HOLDERS + tuple(m for m, _, _ in _READOUT_MODELS):
+        _import_target(name, "readout")
+    for fn in _READOUT_NAMES:
+        _rebind.put_where_held("readout", fn, getattr(readout_compat, fn),
+                               lambda cur: getattr(cur, "__module__", "") == "cogdl.utils.utils")
+    for name, cls_name, fwd in _READOUT_MODELS:
+        _rebind.put("readout", getattr(sys.modules[name], cls_name), "forward", getattr(readout_compat, fwd))
 
 
 _EMB_MODELS = (("cogdl.models.emb.deepwalk", "DeepWalk"), ("cogdl.models.emb.node2vec", "Node2vec"))

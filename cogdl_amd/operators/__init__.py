@@ -10,6 +10,8 @@
     walk.py          random_walk, node2vec_walk (also exported here)   (cogdl/utils/sampling.py, models/emb/node2vec.py)
     ppr.py           topk_ppr, full_ppr (also exported here)           (cogdl/utils/ppr_utils.py)
     sgns.py          skipgram (also exported here)                     (gensim's Word2Vec(sg=1) in models/emb/deepwalk.py)
+    readout.py       segment_ptr, segment_pool, sort_pool (also exported here)   (cogdl/utils/utils.py batch_*_pooling,
+                                                                                  models/nn/gin.py, models/nn/sortpool.py)
 
     ops.py           scatter_add, op_aggr, s_*_e_sum / s_*_e_mean (fused HIP), s_*_e, s_*_t   (cogdl/operators/ops.py)
 
@@ -31,4 +33,8 @@ def __getattr__(name):
         from . import sgns
 
         return sgns.skipgram
+    if name in ("segment_ptr", "segment_pool", "sort_pool"):
+        from . import readout
+
+        return getattr(readout, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -833,6 +833,54 @@ COGDL_API int cogdl_hip_sgns_train(const int64_t *walks, int64_t W, int64_t L, i
                          const float *exp_table, uint64_t seed, int workers, int64_t rows_in_flight, float *syn0,
                          float *syn1, int *flags, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Batched graph readout (csrc/readout.hip): x[N, F] node rows and the sorted `batch` vector of a mini-batch of graphs ->
+ * one row (segment pooling) or k rows (sort-pool) per graph.  Replaces the zeros + scatter_add_ of batch_sum_pooling /
+ * batch_mean_pooling (cogdl/utils/utils.py:192-203) and of GIN's forward (models/nn/gin.py:111-112), the CSR detour of
+ * batch_max_pooling (utils.py:206-221) and the dense pad + sort + gather of SortPool (models/nn/sortpool.py:111-127).
+ * float32, row-major, on `stream`; no atomics, no allocation, no synchronisation, nothing read back.  The order of every
+ * addition and the sort order are csrc/readout_law.h's; the host twins (cogdl_host_*, same names) return the same bytes.
+ *   ptr          int32 [B + 1]: graph g owns the rows [ptr[g], ptr[g + 1]).  A caller's ptr is trusted, but every row index
+ *                is clamped into [0, N]: a malformed ptr gives wrong numbers, never an access outside the arrays.
+ *   segment_ptr  int64 batch[N] with values in [0, B) -> ptr; ids that do not occur get empty segments.  *flag (device
+ *                int, zeroed by the call) becomes non-zero if batch is not non-decreasing or holds a value outside [0, B);
+ *                ptr is then not to be relied on.
+ *   mode         0 sum, 1 mean, 2 max.
+ *     sum        per column, float32 additions in increasing row order starting from +0.0f -- bit for bit what torch's CPU
+ *                scatter_add_ gives -- for segments of up to cogdl_hip_segment_exact_nodes() rows (4096).  A longer segment
+ *                is cut into chunks of 1024 rows dealt round-robin to four accumulators that are added in a fixed order:
+ *                equal from run to run and equal to the host twin, no longer the sequential association.
+ *     mean       that sum, then one division by (float)rows.
+ *     max        the maximum and, in argmax int32 [B, F], its row; ties go to the smallest row.
+ *     An empty segment gives 0 (argmax -1).
+ *     NaN        sum / mean: IEEE propagation.  max: a row is taken only if x > best, starting from -inf, so a NaN is never
+ *                the maximum; a column with nothing above -inf in its segment gives -inf and the segment's first row.
+ *   pool_bwd     grad_x[i, :] from grad[B, F] as a gather, every element of grad_x written once (no zero-fill pass):
+ *                sum grad[g], mean grad[g] / (float)rows, max grad[g, f] where argmax[g, f] == i, else 0.  The graph of
+ *                row i is batch[i] where batch is passed (int64 [N], may be NULL), else found in ptr by binary search.
+ *   sort_pool    per graph the min(k, n_g) rows with the largest x[i, key_col] in descending key order, equal keys in
+ *                increasing row order (-0 equals +0; a NaN key counts as the largest): out [B, k, F], rows past n_g zero;
+ *                idx int32 [B, k] the source rows, -1 there.  One workgroup per graph; graphs of up to
+ *                cogdl_hip_sort_pool_lds_nodes() rows are sorted in LDS, larger ones by counting ranks through the
+ *                workspace (O(n_g^2) comparisons: slow, same result).  workspace: cogdl_hip_sort_pool_workspace_bytes(N)
+ *                bytes, 8-byte aligned (0 for N within the LDS bound: no graph can exceed it).
+ *   sort_pool_bwd  grad_x [N, F] = zeros, then row idx[g, j] = grad[g, j, :] (each node occurs at most once).
+ * N == 0 or B == 0: success, nothing launched.  N, B, F, k, B * k or B * ceil(F / 64) beyond 2^31 - 1: COGDL_HIP_ERANGE.
+ * ------------------------------------------------------------------------------------------------------------------ */
+COGDL_API int cogdl_hip_segment_exact_nodes(void);
+COGDL_API int cogdl_hip_sort_pool_lds_nodes(void);
+COGDL_API int cogdl_hip_segment_ptr(const int64_t *batch, int64_t N, int64_t B, int32_t *ptr, int *flag, void *stream);
+COGDL_API int cogdl_hip_segment_pool_fwd(const float *x, const int32_t *ptr, int64_t N, int64_t B, int64_t F, int mode,
+                               float *out, int32_t *argmax, void *stream);
+COGDL_API int cogdl_hip_segment_pool_bwd(const float *grad, const int32_t *ptr, const int64_t *batch, const int32_t *argmax,
+                               int64_t N, int64_t B, int64_t F, int mode, float *grad_x, void *stream);
+COGDL_API size_t cogdl_hip_sort_pool_workspace_bytes(int64_t N);
+COGDL_API int cogdl_hip_sort_pool_fwd(const float *x, const int32_t *ptr, int64_t N, int64_t B, int64_t F, int64_t k,
+                            int64_t key_col, float *out, int32_t *idx, void *workspace, size_t workspace_bytes,
+                            void *stream);
+COGDL_API int cogdl_hip_sort_pool_bwd(const float *grad, const int32_t *idx, int64_t N, int64_t B, int64_t F, int64_t k,
+                            float *grad_x, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,23 @@ COGDL_HOST_API int cogdl_host_sgns_train(const int64_t *walks, int64_t W, int64_
                                          float *syn0, float *syn1, int *flags, double *trace, int64_t trace_cap,
                                          int64_t *trace_n);
 
+/* Batched graph readout; the host twins of cogdl_hip_segment_ptr / segment_pool_fwd / segment_pool_bwd / sort_pool_fwd /
+ * sort_pool_bwd (include/cogdl_hip.h, where the contract is spelled out): same arguments minus workspace and stream, all
+ * pointers host memory, *flag a host int.  Both sides follow csrc/readout_law.h, so for equal inputs they return EXACTLY the
+ * same arrays in every mode, above cogdl_host_segment_exact_nodes() rows per segment as well.  OpenMP over the graphs; the
+ * result does not depend on the number of threads. */
+COGDL_HOST_API int cogdl_host_segment_exact_nodes(void);
+COGDL_HOST_API int cogdl_host_segment_ptr(const int64_t *batch, int64_t N, int64_t B, int32_t *ptr, int *flag);
+COGDL_HOST_API int cogdl_host_segment_pool_fwd(const float *x, const int32_t *ptr, int64_t N, int64_t B, int64_t F, int mode,
+                                               float *out, int32_t *argmax);
+COGDL_HOST_API int cogdl_host_segment_pool_bwd(const float *grad, const int32_t *ptr, const int64_t *batch,
+                                               const int32_t *argmax, int64_t N, int64_t B, int64_t F, int mode,
+                                               float *grad_x);
+COGDL_HOST_API int cogdl_host_sort_pool_fwd(const float *x, const int32_t *ptr, int64_t N, int64_t B, int64_t F, int64_t k,
+                                            int64_t key_col, float *out, int32_t *idx);
+COGDL_HOST_API int cogdl_host_sort_pool_bwd(const float *grad, const int32_t *idx, int64_t N, int64_t B, int64_t F, int64_t k,
+                                            float *grad_x);
+
 #ifdef __cplusplus
 }
 #endif
