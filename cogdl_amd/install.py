@@ -39,7 +39,8 @@ _finder = None
 
 
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
-            metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False, readout=False):
+            metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False, readout=False,
+            relational=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -88,6 +89,13 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     pad + sort + gather.  No float atomics: sums are equal from run to run, and equal to the reference's CPU sums bit for bit;
     max pooling also runs on the CPU without torch_scatter; equal SortPool keys go in row order.  A batch vector that is
     unsorted or empty, an x that is not 2-D float32, and a mean over absent graph ids go to the reference's own functions.
+    relational=True rebinds CompGCNLayer.message_passing in cogdl.models.nn.compgcn (opt-in: no longer the unchanged layer, and
+    the sums are re-associated -- float32 rounding apart, the same numbers) to cogdl_amd.relational_compat: the typed message
+    passing of the compgcn link-prediction model is one relational aggregation to [N, in] on the library's rel_gspmm operator
+    (HIP kernels for CUDA tensors: no [E, in] / [E, out] message tensors, no float atomics, equal from run to run; the torch
+    composition on the CPU) followed by one [N, in] x [in, out] matmul, instead of a matmul per edge and scatter_add_.  `opn`
+    "sub" and "mult" are served, any other reaches the reference's method.  The reference's RGCNLayer is not served
+    (INTEGRATION.md).
     linear=True additionally routes torch.nn.functional.linear -- i.e. the unchanged nn.Linear inside every CogDL
     layer -- through cogdl_amd.linear (hand-written MFMA weight gradient for full-graph shapes)."""
     global _finder
@@ -149,6 +157,12 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
         _install_skipgram()
     if readout:
         _rebind_readout()
+    if relational:
+        from . import relational_compat
+
+        _import_target("cogdl.models.nn.compgcn", "relational")
+        if not relational_compat.install():
+            raise _lib_error("install(relational=True): CompGCNLayer.message_passing could not be rebound")
     su = sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):

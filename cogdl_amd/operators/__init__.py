@@ -13,6 +13,8 @@
     readout.py       segment_ptr, segment_pool, sort_pool (also exported here)   (cogdl/utils/utils.py batch_*_pooling,
                                                                                   models/nn/gin.py, models/nn/sortpool.py)
 
+    relational.py    rel_gspmm (also exported here)                    (CompGCNLayer.message_passing, models/nn/compgcn.py)
+
     ops.py           scatter_add, op_aggr, s_*_e_sum / s_*_e_mean (fused HIP), s_*_e, s_*_t   (cogdl/operators/ops.py)
 
 Submodules are imported lazily: GPU modules load libcogdl_hip.so at import and raise if it
@@ -37,4 +39,8 @@ def __getattr__(name):
         from . import readout
 
         return getattr(readout, name)
+    if name == "rel_gspmm":
+        from . import relational
+
+        return relational.rel_gspmm
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

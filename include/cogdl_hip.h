@@ -385,6 +385,41 @@ COGDL_API int cogdl_hip_gspmm_edge_grad(const int64_t *row, const int64_t *col, 
                               float *grad_efeat, float *grad_weight, int64_t n_edges, int64_t k, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Relational gspmm (csrc/relspmm.hip): gspmm on a graph whose edges carry a TYPE, the edge operand being a row of a small
+ * relation table looked up through the type -- the message passing of CompGCN (cogdl/models/nn/compgcn.py:124-140: gather
+ * x[col], gather rel_embed[edge_type], combine, multiply by the layer weight, scale, scatter_add_) without any [E, k] tensor
+ * and without atomics.  Over the destination-sorted (CSR) view of the edges:
+ *   out[v,:] = sum_{j in row v} weight[id_j] * ( x[colind[j],:] OP rel[etype[id_j],:] ),   id_j = eid ? eid[j] : j
+ *   eid     CSR position -> edge id of etype/weight (perm of cogdl_hip_coo2csr_index, as int32), NULL = identity;
+ *   etype   [E] int32 in the caller's edge order, every id in [0, n_rel) (the kernel clamps: a bad id gives a wrong
+ *           number, not a read outside rel; the Python front refuses it before the launch);
+ *   x       [n_src, k];   rel [n_rel, k] or NULL (message = the source row alone, etype unused);   weight [E] or NULL;
+ *   op      COGDL_HIP_GSPMM_ADD | SUB | MUL | WMUL (WMUL: (x * weight) * rel, autograd's rounding order for the source
+ *           gradient of MUL: x := the upstream gradient rows over the SOURCE-sorted view; SUB / ADD take rel = NULL there).
+ * fp32; per output element the edges are added in row order with every step rounded like the torch expression, so rows
+ * of up to cogdl_hip_exact_row_edges(nnz) edges equal a sequential CPU scatter_add_ bit for bit; longer rows are summed
+ * in pieces merged in a fixed order.  No atomics (deterministic).  Vector width 4 -> 2 -> 1 by pointer alignment and k.
+ * ------------------------------------------------------------------------------------- */
+COGDL_API size_t cogdl_hip_rel_gspmm_workspace_bytes(int64_t nnz, int64_t k);
+COGDL_API int cogdl_hip_rel_gspmm(const int32_t *rowptr, const int32_t *colind, const int32_t *eid, const int32_t *etype,
+                        const float *x, const float *rel, const float *weight, int op, float *out, int64_t m, int64_t k,
+                        int64_t nnz, int64_t n_rel, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Gradient of the relation table, over the TYPE-sorted view of the same edges (typeptr [n_rel + 1]; stable sort, so the
+ * edges of a type keep the caller's order), from the upstream gradient grad [m, k]:
+ *   grad_rel[t,:] = sum_{j in row t}  SUB: -(grad[dst_j,:] * weight[id_j])   ADD: grad[dst_j,:] * weight[id_j]
+ *                                     MUL: (grad[dst_j,:] * weight[id_j]) * x[src_j,:]
+ *   dst_sorted / src_sorted  [E] destination / source of every edge in sorted order (src_sorted and x: MUL only);
+ *   eid     sorted position -> edge id of weight, NULL = identity;   op: COGDL_HIP_GSPMM_ADD | SUB | MUL.
+ * Same engine, same summation rules; a type without edges gives a zero row.  The rows are long by construction (E / n_rel
+ * edges), so the chunk path with its fixed merge order is the usual one: deterministic, re-associated. */
+COGDL_API size_t cogdl_hip_rel_gspmm_grad_rel_workspace_bytes(int64_t nnz, int64_t k);
+COGDL_API int cogdl_hip_rel_gspmm_grad_rel(const int32_t *typeptr, const int32_t *dst_sorted, const int32_t *src_sorted,
+                                 const int32_t *eid, const float *grad, const float *x, const float *weight, int op,
+                                 float *grad_rel, int64_t n_rel, int64_t k, int64_t nnz, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Fused GAT attention + aggregation (no [E,H] tensor is materialised in forward):
  *   s[e,h] = LeakyReLU(attn_row[row(e),h] + attn_col[colind[e],h]);  a = softmax_row(s)
  *   out[v,h,:] = sum_e a[e,h] * feat[colind[e],h,:]
