@@ -40,7 +40,7 @@ _finder = None
 
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
             metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False, readout=False,
-            relational=False):
+            relational=False, genconv=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -96,6 +96,13 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     composition on the CPU) followed by one [N, in] x [in, out] matmul, instead of a matmul per edge and scatter_add_.  `opn`
     "sub" and "mult" are served, any other reaches the reference's method.  The reference's RGCNLayer is not served
     (INTEGRATION.md).
+    genconv=True rebinds GENConv.forward in cogdl.layers.deepergcn_layer (opt-in: no longer the unchanged layer, and the softmax
+    sums are re-associated -- float32 rounding apart, the same numbers) to cogdl_amd.genconv_compat: the aggregation of the
+    deepergcn and revgcn models (gather, edge encoder term, relu + eps, beta, per-column edge softmax, multiply, scatter_add_)
+    is one call of the library's gen_aggregate operator (HIP kernels for CUDA tensors: no [E, F] message tensors, no float
+    atomics, equal from run to run; the torch composition on the CPU).  `softmax_sg`, `softmax`, `mean` and the plain sum are
+    served; `powermean`, `max`, a graph without a CSR and a graph whose CSR does not describe its edge_index reach the
+    reference's forward.
     linear=True additionally routes torch.nn.functional.linear -- i.e. the unchanged nn.Linear inside every CogDL
     layer -- through cogdl_amd.linear (hand-written MFMA weight gradient for full-graph shapes)."""
     global _finder
@@ -163,6 +170,12 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
         _import_target("cogdl.models.nn.compgcn", "relational")
         if not relational_compat.install():
             raise _lib_error("install(relational=True): CompGCNLayer.message_passing could not be rebound")
+    if genconv:
+        from . import genconv_compat
+
+        _import_target("cogdl.layers.deepergcn_layer", "genconv")
+        if not genconv_compat.install():
+            raise _lib_error("install(genconv=True): GENConv.forward could not be rebound")
     su = sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):

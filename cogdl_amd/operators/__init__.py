@@ -15,6 +15,8 @@
 
     relational.py    rel_gspmm (also exported here)                    (CompGCNLayer.message_passing, models/nn/compgcn.py)
 
+    genaggr.py       gen_aggregate (also exported here)                (GENConv.forward, layers/deepergcn_layer.py:67-93)
+
     ops.py           scatter_add, op_aggr, s_*_e_sum / s_*_e_mean (fused HIP), s_*_e, s_*_t   (cogdl/operators/ops.py)
 
 Submodules are imported lazily: GPU modules load libcogdl_hip.so at import and raise if it
@@ -43,4 +45,8 @@ def __getattr__(name):
         from . import relational
 
         return relational.rel_gspmm
+    if name == "gen_aggregate":
+        from . import genaggr
+
+        return genaggr.gen_aggregate
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -420,6 +420,45 @@ COGDL_API int cogdl_hip_rel_gspmm_grad_rel(const int32_t *typeptr, const int32_t
                                  size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * GENConv aggregation (csrc/genaggr.hip): the message passing of DeeperGCN's layer (cogdl/layers/deepergcn_layer.py:67-93:
+ * gather x[col], add the encoded edge features, relu + eps, times beta, edge softmax with one channel per column, multiply,
+ * scatter_add_) without any [E, k] tensor and without atomics.  Over the destination-sorted (CSR) view of the edges:
+ *   msg[j,:]  = relu(x[colind[j],:] + eterm[id_j,:]) + eps,                          id_j = eid ? eid[j] : j
+ *   SOFTMAX:    out[v,:] = sum_{j in row v} softmax_{j in row v}(beta * msg[j,:]) * msg[j,:]     (per column)
+ *   SUM / MEAN: out[v,:] = sum_{j in row v} w_v * msg[j,:],   w_v = 1 | 1 / deg(v) (0 for an empty row); the product is
+ *               rounded before the add, so rows of up to cogdl_hip_exact_row_edges(nnz) edges equal a sequential CPU
+ *               scatter_add_ of msg * deg_rev[row] bit for bit.
+ *   eterm     [E, k] in the caller's edge order, or NULL;   eid as for cogdl_hip_rel_gspmm;
+ *   beta_dev  one float in device memory (read by the kernel: nothing is baked into a captured graph), or NULL: `beta`;
+ *   lse       [m, k] or NULL: max + log(denom) of every (row, column), what the backward needs (0 for an empty row);
+ *   q         [m, k] or NULL (needs lse): sum_j softmax_j * msg_j^2, from which the caller takes the gradient of beta,
+ *             sum(grad * (q - out^2)).  lse and q are SOFTMAX only (COGDL_HIP_EINVAL otherwise).
+ * The softmax is an online softmax in CSR edge order (one expf per edge and column); rows longer than the long-row
+ * threshold are reduced in pieces whose states merge with the usual rescaling in a fixed order.  A row of one edge returns
+ * msg bit for bit, an empty row 0.  fp32, deterministic.  Vector width 4 -> 2 -> 1 by pointer alignment and k.
+ * ------------------------------------------------------------------------------------- */
+enum { COGDL_HIP_GEN_SOFTMAX = 0, COGDL_HIP_GEN_SUM = 1, COGDL_HIP_GEN_MEAN = 2 };
+COGDL_API size_t cogdl_hip_gen_aggr_fwd_workspace_bytes(int64_t nnz, int64_t k);
+COGDL_API int cogdl_hip_gen_aggr_fwd(const int32_t *rowptr, const int32_t *colind, const int32_t *eid, const float *x,
+                           const float *eterm, int mode, const float *beta_dev, float beta, float eps, float *out,
+                           float *lse, float *q, int64_t m, int64_t k, int64_t nnz, void *workspace,
+                           size_t workspace_bytes, void *stream);
+
+/* Backward over the SOURCE-sorted view of the same edges (srcptr [n_src + 1]; dst_sorted [E] the destination of every edge
+ * in that order; eid sorted position -> edge id of eterm / grad_eterm, NULL = identity):
+ *   pre = x[u,:] + eterm[id,:],  msg = relu(pre) + eps,  s = exp(beta * msg - lse[v,:])
+ *   SOFTMAX:    d = grad[v,:] * s * (1 + beta * (msg - out[v,:])) * [pre > 0]
+ *   SUM / MEAN: d = grad[v,:] * [pre > 0]            (MEAN: the caller passes grad already multiplied by 1 / deg(v))
+ *   grad_x[u,:] = sum of d over the out-edges of u in the caller's edge order (pieces in a fixed order for long rows);
+ *   grad_eterm[id,:] = d when grad_eterm != NULL ([E, k]: every row is written exactly once).
+ * out / lse: the forward's results (SOFTMAX only).  No atomics. */
+COGDL_API size_t cogdl_hip_gen_aggr_bwd_workspace_bytes(int64_t nnz, int64_t k);
+COGDL_API int cogdl_hip_gen_aggr_bwd(const int32_t *srcptr, const int32_t *dst_sorted, const int32_t *eid, const float *x,
+                           const float *eterm, const float *grad, const float *out, const float *lse, int mode,
+                           const float *beta_dev, float beta, float eps, float *grad_x, float *grad_eterm, int64_t n_src,
+                           int64_t k, int64_t nnz, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Fused GAT attention + aggregation (no [E,H] tensor is materialised in forward):
  *   s[e,h] = LeakyReLU(attn_row[row(e),h] + attn_col[colind[e],h]);  a = softmax_row(s)
  *   out[v,h,:] = sum_e a[e,h] * feat[colind[e],h,:]
