@@ -72,6 +72,13 @@ HIP_SIGNATURES = {
     "cogdl_hip_gen_aggr_fwd": ([_vp] * 5 + [_i32, _vp, _f32, _f32] + [_vp] * 3 + [_i64, _i64, _i64, _vp, _sz, _vp], _i32),
     "cogdl_hip_gen_aggr_bwd_workspace_bytes": ([_i64, _i64], _sz),
     "cogdl_hip_gen_aggr_bwd": ([_vp] * 8 + [_i32, _vp, _f32, _f32, _vp, _vp, _i64, _i64, _i64, _vp, _sz, _vp], _i32),
+    # neighbourhood routing (csrc/disen.hip)
+    "cogdl_hip_disen_route_fwd_workspace_bytes": ([_i64, _i64, _i64], _sz),
+    "cogdl_hip_disen_route_fwd": ([_vp] * 4 + [_f32] + [_vp] * 3 + [_i64, _i64, _i64, _i64, _vp, _sz, _vp], _i32),
+    "cogdl_hip_disen_route_bwd_c_workspace_bytes": ([_i64, _i64, _i64], _sz),
+    "cogdl_hip_disen_route_bwd_c": ([_vp] * 7 + [_f32, _vp, _i64, _i64, _i64, _i64, _vp, _sz, _vp], _i32),
+    "cogdl_hip_disen_route_bwd_z_workspace_bytes": ([_i64, _i64, _i64], _sz),
+    "cogdl_hip_disen_route_bwd_z": ([_vp] * 7 + [_f32, _vp, _i64, _i64, _i64, _i64, _vp, _sz, _vp], _i32),
     "cogdl_hip_gat_fwd_workspace_bytes": ([_i64, _i64, _i64, _i32], _sz),
     "cogdl_hip_gat_fwd": ([_vp] * 5 + [_f32] + [_vp] * 3 + [_i64, _i64, _i64, _i64, _i32, _vp, _sz, _vp], _i32),
     "cogdl_hip_gat_bwd_workspace_bytes": ([_i64, _i64, _i64, _i64, _i64, _i32], _sz),

@@ -40,7 +40,7 @@ _finder = None
 
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
             metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False, readout=False,
-            relational=False, genconv=False):
+            relational=False, genconv=False, disengcn=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -103,6 +103,13 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     atomics, equal from run to run; the torch composition on the CPU).  `softmax_sg`, `softmax`, `mean` and the plain sum are
     served; `powermean`, `max`, a graph without a CSR and a graph whose CSR does not describe its edge_index reach the
     reference's forward.
+    disengcn=True rebinds DisenGCNLayer.forward in cogdl.layers.disengcn_layer (opt-in: no longer the unchanged layer, and the
+    softmax sums are re-associated -- float32 rounding apart, the same numbers) to cogdl_amd.disengcn_compat: the channel
+    normalisation and the routing loop of the disengcn model (per iteration three [E, K, d] gathers, a K-head edge softmax, an
+    int64 [K, E, d] index and scatter_add_) are one call of the library's neighbor_routing (per iteration one disen_route
+    operator; HIP kernels for CUDA tensors with d in {2, .., 64}: nothing of size [E, .] is written, no float atomics, equal
+    from run to run; the torch composition on the CPU).  A graph without a CSR, a graph whose CSR does not describe its
+    edge_index, an x that is not 2-D and an out_feats that K does not divide reach the reference's forward.
     linear=True additionally routes torch.nn.functional.linear -- i.e. the unchanged nn.Linear inside every CogDL
     layer -- through cogdl_amd.linear (hand-written MFMA weight gradient for full-graph shapes)."""
     global _finder
@@ -176,6 +183,12 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
         _import_target("cogdl.layers.deepergcn_layer", "genconv")
         if not genconv_compat.install():
             raise _lib_error("install(genconv=True): GENConv.forward could not be rebound")
+    if disengcn:
+        from . import disengcn_compat
+
+        _import_target("cogdl.layers.disengcn_layer", "disengcn")
+        if not disengcn_compat.install():
+            raise _lib_error("install(disengcn=True): DisenGCNLayer.forward could not be rebound")
     su = sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):

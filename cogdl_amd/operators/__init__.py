@@ -17,6 +17,8 @@
 
     genaggr.py       gen_aggregate (also exported here)                (GENConv.forward, layers/deepergcn_layer.py:67-93)
 
+    disen.py         disen_route, neighbor_routing (also exported here)  (DisenGCNLayer.forward, layers/disengcn_layer.py:48-69)
+
     ops.py           scatter_add, op_aggr, s_*_e_sum / s_*_e_mean (fused HIP), s_*_e, s_*_t   (cogdl/operators/ops.py)
 
 Submodules are imported lazily: GPU modules load libcogdl_hip.so at import and raise if it
@@ -49,4 +51,8 @@ def __getattr__(name):
         from . import genaggr
 
         return genaggr.gen_aggregate
+    if name in ("disen_route", "neighbor_routing"):
+        from . import disen
+
+        return getattr(disen, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

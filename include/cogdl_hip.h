@@ -459,6 +459,42 @@ COGDL_API int cogdl_hip_gen_aggr_bwd(const int32_t *srcptr, const int32_t *dst_s
                            int64_t k, int64_t nnz, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Neighbourhood routing (csrc/disen.hip): one step of DisenGCN's routing loop (cogdl/layers/disengcn_layer.py:56-69) without
+ * any [E, K d] or [E, K] tensor and without atomics.  c, z, out: [n, n_channels * d], channel k = columns k d .. (k + 1) d - 1.
+ * Over the destination-sorted (CSR) view of the edges (rowptr [n + 1], colind [nnz] = the source of every edge):
+ *   s[e,k]   = <c[i,k], z[j,k]> / tau                                           (i the row, j = colind[e])
+ *   a[i,k]   = z[i,k] + sum_{e in row i} softmax_{e in row i}(s[e,k]) * z[j,k]      (a row without edges: z[i,k])
+ *   out[i,k] = a[i,k] / nrm[i,k],   nrm[i,k] = ||a[i,k]||_2                     (no epsilon: a zero a[i,k] gives nan)
+ *   nrm, lse [n, n_channels]: the norm, and max + log(denom) of the softmax (0 for a row without edges; lse may be NULL).
+ * d in {2, 4, 8, 16, 32, 64} (anything else: COGDL_HIP_EUNSUPPORTED), any n_channels >= 1, tau > 0.  The softmax is an online
+ * softmax in CSR edge order (one expf per edge and channel); rows longer than the long-row threshold are reduced in pieces
+ * whose states merge with the usual rescaling in a fixed order.  fp32, deterministic.  Vector width 4 -> 2 -> 1 by pointer
+ * alignment, row length and d; the workspace covers every width.
+ * ------------------------------------------------------------------------------------- */
+COGDL_API size_t cogdl_hip_disen_route_fwd_workspace_bytes(int64_t nnz, int64_t n_channels, int64_t d);
+COGDL_API int cogdl_hip_disen_route_fwd(const int32_t *rowptr, const int32_t *colind, const float *c, const float *z, float tau,
+                              float *out, float *nrm, float *lse, int64_t n, int64_t n_channels, int64_t d, int64_t nnz,
+                              void *workspace, size_t workspace_bytes, void *stream);
+
+/* Backward.  The caller supplies ga = d loss / d a = (g - out <out, g>) / nrm  [n, n_channels * d]  and
+ * dl[i,k] = <ga[i,k], nrm[i,k] out[i,k] - z[i,k]>  [n, n_channels].  Per edge both passes recompute
+ *   p = exp(s - lse[i,k]),  t = <ga[i,k], z[j,k]>,  r = p * (t - dl[i,k]) / tau            (no per-edge scratch)
+ * bwd_c, over the destination-sorted view of the forward:  grad_c[i,k] = sum_{e in row i} r * z[j,k];
+ * bwd_z, over the SOURCE-sorted view (srcptr [n + 1]; dst_sorted [nnz] the destination of every edge in that order):
+ *   grad_z[j,k] = ga[j,k] + sum_{e: source j} (p * ga[i,k] + r * c[i,k]).
+ * Sums in the view's edge order (pieces in a fixed order for long rows).  No atomics. */
+COGDL_API size_t cogdl_hip_disen_route_bwd_c_workspace_bytes(int64_t nnz, int64_t n_channels, int64_t d);
+COGDL_API int cogdl_hip_disen_route_bwd_c(const int32_t *rowptr, const int32_t *colind, const float *c, const float *z,
+                                const float *ga, const float *lse, const float *dl, float tau, float *grad_c, int64_t n,
+                                int64_t n_channels, int64_t d, int64_t nnz, void *workspace, size_t workspace_bytes,
+                                void *stream);
+COGDL_API size_t cogdl_hip_disen_route_bwd_z_workspace_bytes(int64_t nnz, int64_t n_channels, int64_t d);
+COGDL_API int cogdl_hip_disen_route_bwd_z(const int32_t *srcptr, const int32_t *dst_sorted, const float *c, const float *z,
+                                const float *ga, const float *lse, const float *dl, float tau, float *grad_z, int64_t n,
+                                int64_t n_channels, int64_t d, int64_t nnz, void *workspace, size_t workspace_bytes,
+                                void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Fused GAT attention + aggregation (no [E,H] tensor is materialised in forward):
  *   s[e,h] = LeakyReLU(attn_row[row(e),h] + attn_col[colind[e],h]);  a = softmax_row(s)
  *   out[v,h,:] = sum_e a[e,h] * feat[colind[e],h,:]
