@@ -40,7 +40,7 @@ _finder = None
 
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
             metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False, readout=False,
-            relational=False, genconv=False, disengcn=False):
+            relational=False, genconv=False, disengcn=False, contrast=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -110,6 +110,13 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     operator; HIP kernels for CUDA tensors with d in {2, .., 64}: nothing of size [E, .] is written, no float atomics, equal
     from run to run; the torch composition on the CPU).  A graph without a CSR, a graph whose CSR does not describe its
     edge_index, an x that is not 2-D and an out_feats that K does not divide reach the reference's forward.
+    contrast=True rebinds GRACEModelWrapper.contrastive_loss in cogdl.wrappers.model_wrapper.node_classification.grace_mw (opt-in:
+    no longer the unchanged wrapper, and the row sums are re-associated -- float32 rounding apart, the same numbers) to
+    cogdl_amd.contrast_compat: the loss of the grace model is one call of the library's grace_loss (normalisation, then the
+    pair_lse operator: a torch composition in row blocks of the queries whose backward recomputes the scores, so neither of
+    the two [N, N] score matrices is kept; there is no HIP kernel behind it, GPU tensors run torch's kernels and say so once
+    with a TorchRouteWarning).  batched_loss calls the rebound method and is served as it stands.  Inputs that are not 2-D
+    float tensors of one width reach the reference's method.
     linear=True additionally routes torch.nn.functional.linear -- i.e. the unchanged nn.Linear inside every CogDL
     layer -- through cogdl_amd.linear (hand-written MFMA weight gradient for full-graph shapes)."""
     global _finder
@@ -189,6 +196,12 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
         _import_target("cogdl.layers.disengcn_layer", "disengcn")
         if not disengcn_compat.install():
             raise _lib_error("install(disengcn=True): DisenGCNLayer.forward could not be rebound")
+    if contrast:
+        from . import contrast_compat
+
+        _import_target(contrast_compat._MODULE, "contrast")
+        if not contrast_compat.install():
+            raise _lib_error("install(contrast=True): GRACEModelWrapper.contrastive_loss could not be rebound")
     su = sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):

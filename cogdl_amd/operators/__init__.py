@@ -19,6 +19,9 @@
 
     disen.py         disen_route, neighbor_routing (also exported here)  (DisenGCNLayer.forward, layers/disengcn_layer.py:48-69)
 
+    contrast.py      pair_lse, grace_loss (also exported here)         (GRACEModelWrapper.contrastive_loss,
+                                                                        wrappers/model_wrapper/node_classification/grace_mw.py:64-77)
+
     ops.py           scatter_add, op_aggr, s_*_e_sum / s_*_e_mean (fused HIP), s_*_e, s_*_t   (cogdl/operators/ops.py)
 
 Submodules are imported lazily: GPU modules load libcogdl_hip.so at import and raise if it
@@ -55,4 +58,8 @@ def __getattr__(name):
         from . import disen
 
         return getattr(disen, name)
+    if name in ("pair_lse", "grace_loss"):
+        from . import contrast
+
+        return getattr(contrast, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
