@@ -13,7 +13,8 @@ int g_tuning[kTuneCount] = {/*0: xcd stripe*/ 32, /*1: long-row threshold overri
                             /*14: retired (round 4's csr_spmm row tiles, removed in round 6)*/ 0,
                             /*15: 64-bit CSR: edges per row segment (0 = default 2^29; tests use tiny values)*/ 0,
                             /*16: retired (round 5's per-workgroup row queue, removed in round 6)*/ 0,
-                            /*17: sgns row update: 0 = memory-side atomicAdd(float), 1 = write-through read-modify-write stores*/ 0};
+                            /*17: sgns row update: 0 = memory-side atomicAdd(float), 1 = write-through read-modify-write stores*/ 0,
+                            /*18: csr_spmm sweep: cap on the rows of one round (0 = what the device holds; tests use small values)*/ 0};
 }
 
 namespace cogdl {

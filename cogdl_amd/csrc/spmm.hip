@@ -21,6 +21,7 @@
 // re-association, <= 1e-6 relative).
 // HBM-bound: algorithmic bytes per edge = 4 (colind) + s_w + F*s, per row 4 + F*s.
 #include "spmm_op.h"
+#include "rowsweep.h"
 
 namespace cogdl {
 
@@ -205,6 +206,36 @@ extern "C" int cogdl_hip_csr_spmm_xcd(const cogdl_hip_vrows *plan, const void *v
             return spmm_xcd_typed<__hip_bfloat16>(plan, val_plan, x, out, m, k, acc, workspace, workspace_bytes, s);
         default: return COGDL_HIP_EDTYPE;
     }
+}
+
+// ---- sweep layout of a column-sorted structure (rowsweep.h) -----------------------------------------------------------------
+extern "C" int cogdl_hip_csr_spmm_sweep_group_rows(void) { return kSweepRows; }
+
+extern "C" int64_t cogdl_hip_csr_spmm_sweep_round_rows(int64_t k, int dtype) {
+    if (dtype != COGDL_HIP_F32 || k != 2 * kWave) return 0;  // (rows of 512 bytes: one float2 per lane)
+    return sweep_round_waves() * kSweepRows;
+}
+
+extern "C" int cogdl_hip_csr_spmm_sweep(const int32_t *goff, const int32_t *src, const void *w, const void *x, void *out,
+                                        int64_t m, int64_t n_src, int64_t n_groups, int r, int64_t k, int64_t nnz, int dtype, void *stream) {
+    if (m < 0 || n_groups < 0 || nnz < 0 || r < 1 || r > kSweepRows) return COGDL_HIP_EINVAL;
+    if (dtype != COGDL_HIP_F32 || k != 2 * kWave) return COGDL_HIP_EUNSUPPORTED;
+    if (m == 0) return COGDL_HIP_OK;
+    if (n_groups != (m + r - 1) / r) return COGDL_HIP_EINVAL;
+    if (!goff || !x || !out || (nnz > 0 && !src)) return COGDL_HIP_EINVAL;
+    if (nnz > COGDL_HIP_SEGMENT_MAX_EDGES) return COGDL_HIP_ERANGE;
+    if (!aligned_to(x, sizeof(float2)) || !aligned_to(out, sizeof(float2))) return COGDL_HIP_EALIGN;
+    if (n_src <= 0 || n_src > (1 << 23)) return COGDL_HIP_EUNSUPPORTED;  // (24-bit rows, 32-bit byte offsets into x)
+    const int64_t waves = sweep_round_waves();
+    if (waves <= 0) {
+        g_last_hip_error = (int)hipGetLastError();
+        return COGDL_HIP_ELAUNCH;
+    }
+    SweepArgs a{goff, (const uint32_t *)src, (const float *)w, (const float *)x, (float *)out, m, n_groups, r, (uint32_t)(k * sizeof(float))};
+    const unsigned blocks = (unsigned)((std::min(waves, n_groups) + 3) / 4);
+    if (w) hipLaunchKernelGGL((rowreduce_sweep_kernel<true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((rowreduce_sweep_kernel<false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+    return launch_status();
 }
 
 // ---- 64-bit CSR: one launch per row segment (bigcsr.hip) ---------------------------------------------------------------

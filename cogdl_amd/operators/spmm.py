@@ -141,6 +141,40 @@ def csr_spmm_xcd_raw(xplan, val, x, out=None):
     return out
 
 
+def csr_spmm_sweep_raw(csc, val, x):
+    """A^T x over the sweep layout of the transpose `csc` (a plan.CscPlan; cogdl_amd/sweepplan.py, cogdl_hip_csr_spmm_sweep):
+    `val` in the CALLER's CSR edge order or None; fp32, 128 columns.  Bit-identical to csr_spmm_raw(csc.colptr, csc.rowind,
+    csc.transposed_values(val), x) where the transpose has no row beyond the exact-row bound."""
+    from .. import sweepplan
+
+    dev = _lib.require_cuda(csc.colptr, val, x)
+    if x.dim() != 2 or x.dtype != torch.float32 or x.shape[0] != csc.m:
+        raise _lib.BackendError("csr_spmm_sweep: the dense operand must be a float32 [%d, k] tensor" % csc.m)
+    x = x.contiguous()
+    k = x.shape[1]
+    sp = sweepplan.of(csc, k, x.dtype)
+    if val is not None:
+        if val.numel() != csc.nnz:
+            raise _lib.BackendError("csr_data has %d entries for %d edges" % (val.numel(), csc.nnz))
+        val = sweepplan.values(csc, val.contiguous() if val.dtype == x.dtype else val.to(x.dtype))
+    out = torch.empty((csc.n_cols, k), dtype=x.dtype, device=dev)
+    with _lib.on_device(dev):
+        pair = None
+        if KERNEL_EVENTS is not None:
+            pair = (KERNEL_EVENTS.take() if hasattr(KERNEL_EVENTS, "take")
+                    else (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+        if pair is not None:
+            pair[0].record()
+        rc = _lib.hip().cogdl_hip_csr_spmm_sweep(_lib.ptr(sp.goff), _lib.ptr(sp.src), _lib.ptr(val), _lib.ptr(x), _lib.ptr(out),
+                                                 csc.n_cols, csc.m, sp.n_groups, sp.r, k, sp.nnz, _lib.DTYPE_CODE[x.dtype],
+                                                 _lib.stream_of(x))
+        if pair is not None:
+            pair[1].record()
+            KERNEL_EVENTS.append(pair)
+    _lib.check(rc, "csr_spmm_sweep")
+    return out
+
+
 def csr_sddmm_raw(rowptr, colind, d1, d2):
     """out[e] = <d1[row(e)], d2[col[e]]>  (fp32)."""
     dev = _lib.require_cuda(rowptr, colind, d1, d2)
@@ -198,6 +232,8 @@ class SPMMFunction(torch.autograd.Function):
                 if split_t is not None:
                     # (w stays in CSR order: the plan of the transpose maps its positions through the transpose's perm)
                     grad_feat = csr_spmm_xcd_raw(xplan_t, w, grad_out)
+                elif xcdplan.spmm_backward_sweep(plan, grad_out):
+                    grad_feat = csr_spmm_sweep_raw(plan, w, grad_out)  # (w stays in CSR order: the layout composes the perm)
                 else:
                     w_t = plan.transposed_values(w) if w is not None else None
                     grad_feat = csr_spmm_raw(plan.colptr, plan.rowind, w_t, grad_out, split_long_rows=plan.has_hub_columns())

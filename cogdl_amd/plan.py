@@ -26,7 +26,7 @@ from . import _lib
 
 class CscPlan:
     __slots__ = ("colptr", "rowind", "perm", "m", "n_cols", "nnz", "_val_key", "_val_src", "_val_t",
-                 "_max_col_degree", "ready", "_ws", "sightings")
+                 "_max_col_degree", "ready", "_ws", "sightings", "sweep")
 
     def __init__(self, colptr, rowind, perm, m, n_cols, nnz):
         self.colptr, self.rowind, self.perm = colptr, rowind, perm
@@ -35,6 +35,7 @@ class CscPlan:
         self._max_col_degree = None
         self.ready, self._ws = None, None  # (csr2csc(stream=...): the event to wait for, the workspace kept until then)
         self.sightings = 1  # cache look-ups that found this structure (PlanCache._lookup): > 1 = a structure that comes back
+        self.sweep = None   # the sweep layout of this transpose (cogdl_amd/sweepplan.py), built on first use
 
     def has_hub_columns(self):
         """Does A^T have rows beyond the long-row threshold?  (One reduction + sync, once per plan.)  When it does not,
@@ -61,7 +62,7 @@ class CscPlan:
         return self._val_t
 
     def nbytes(self):
-        return 4 * (self.colptr.numel() + self.rowind.numel() + self.perm.numel())
+        return 4 * (self.colptr.numel() + self.rowind.numel() + self.perm.numel()) + (self.sweep.nbytes() if self.sweep is not None else 0)
 
 
 def tensor_key(t):
@@ -449,6 +450,16 @@ class PlanCache:
                 _, old = self.lru.popitem(last=False)
                 self.bytes -= old.nbytes()
         return plan
+
+    def grew(self, plan, delta):
+        """A cached plan grew by `delta` bytes after it was stored (its sweep layout, the layout's memoised weights): count them,
+        and evict from the cold end as a store would."""
+        if not delta or not any(p is plan for p in self.lru.values()):
+            return
+        self.bytes += delta
+        while self.bytes > self.budget and len(self.lru) > 1:
+            _, old = self.lru.popitem(last=False)
+            self.bytes -= old.nbytes()
 
     def clear(self):
         self.lru.clear()

@@ -325,6 +325,35 @@ def spmm_backward(fp, csc, grad_out, took_plan):
     return _plan.taped_choice("csr_spmm.backward", decide)
 
 
+SWEEP_ROW_BYTES = 512            # fp32 F = 128: the one width the sweep kernel takes (csrc/rowsweep.h)
+SWEEP_MIN_TABLE_BYTES = 32 << 20  # below: the gathered table fits the eight L2s together, the ordinary launch already hits
+
+
+def spmm_backward_sweep(csc, grad_out, round_rows=None):
+    """SPMMFunction.backward, asked only when spmm_backward said "ordinary": does the launch over the transpose `csc` (a
+    plan.CscPlan) walk its sweep layout (cogdl_amd/sweepplan.py: every wave walks the gathered table top to bottom, bit-identical
+    results)?  fp32 2-D operands of 512-byte rows; a table beyond the eight L2s and of at most 2^23 rows; a transpose without
+    hub rows (the sweep reduces every row sequentially); from the structure's SECOND sighting on (a one-off never pays the
+    layout's sort); MODE auto only; never for transient structures or under a plan tape (captured steps keep the ordinary
+    launch); and only while all rows fit ONE round of the grid -- with two rounds the second starts when the first wave
+    finishes, not when the table's top comes round again, and the ideal hit rate drops from 0.54 to 0.35.
+    round_rows: rows of one round for this width (default: asked of the library, which asks the device)."""
+    if MODE != "auto" or _plan.transient() or _plan.taping():
+        return False
+    if grad_out.dim() != 2 or grad_out.dtype != torch.float32 or grad_out.shape[1] * grad_out.element_size() != SWEEP_ROW_BYTES:
+        return False
+    from . import sweepplan
+
+    n_src = grad_out.shape[0]
+    if csc.sightings < 2 or csc.nnz == 0 or n_src > sweepplan.MAX_TABLE_ROWS or n_src * SWEEP_ROW_BYTES < SWEEP_MIN_TABLE_BYTES:
+        return False
+    if round_rows is None:
+        round_rows = sweepplan.round_rows(grad_out.shape[1], grad_out.dtype)
+    if csc.n_cols > round_rows:
+        return False
+    return not csc.has_hub_columns()
+
+
 def gat_forward(fp, rowptr, colind, n_src, row_bytes):
     """FusedGATFunction.forward -> the structure's plan (cut at SPLIT) or None.  row_bytes: None for an operand the kernels refuse.
     H; else S -- a memoised structure and the recorded eager run of cogdl_amd.graphs.capture wait for the key."""

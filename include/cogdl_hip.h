@@ -77,7 +77,7 @@ COGDL_API int cogdl_hip_last_hip_error(void);
  *   10  csr2csc (0 = by size: one single-workgroup launch up to 16 k slots, the radix sort above; 2 = the radix sort at
  *       every size; 3 = with packed intermediate records at every size)
  *   11  sampler relabelling (1 = the sort-based form)       13  timing: 1 = row blocks exit, 2 = long-row workgroups exit (WRONG results)
- *   15  64-bit CSR: edges per row segment (0 = 2^29)
+ *   15  64-bit CSR: edges per row segment (0 = 2^29)       18  csr_spmm sweep: cap on the rows of one round (0 = the device's)
  *   12, 14, 16  retired in round 6 (wave-scope split of medium rows, row tiles, per-workgroup row queue: all measured <= +-5 %). */
 COGDL_API int cogdl_hip_set_tuning(int key, int value);
 /* Measurement hook (bench.py `roofline.measured_read_GBs`, SURVEY.md section 8d: the box's own roof beside the spec
@@ -154,6 +154,28 @@ COGDL_API size_t cogdl_hip_csr_spmm_xcd_workspace_bytes(int64_t n_parts, int64_t
 COGDL_API int cogdl_hip_csr_spmm_xcd(const cogdl_hip_vrows *plan, const void *val_plan, const void *x, void *out,
                                      int64_t m, int64_t k, int dtype, int acc, void *workspace, size_t workspace_bytes,
                                      void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Sweep layout (added within ABI v9: new symbols only, nothing existing changes; no reference counterpart): out = A x for a
+ * structure whose rows list their columns in ASCENDING order -- the
+ * stable transpose that the backward pass of csr_spmm runs over -- with the edges of every group of r consecutive rows merged
+ * in ascending column order (stable: equal columns keep their CSR order).  One wave owns a group and keeps its rows' states on chip --
+ * registers and LDS -- while it walks the table x top to bottom; with every wave of the chip doing so at about the same pace, the rows an
+ * XCD gathers at any moment share a few MB of x (its private L2).  No wave waits for another: the pace only affects speed.
+ * Every row still sees its own edges in CSR order, so the result is bit-identical to cogdl_hip_csr_spmm on the same structure.
+ *   goff [n_groups + 1]   edge offsets of the groups in layout order, n_groups = ceil(m / r)
+ *   src  [nnz]            per edge: column (low 24 bits; x: [n_src, k] with n_src <= 2^23, else COGDL_HIP_EUNSUPPORTED) |
+ *                         row - g * r (high 8 bits)
+ *   w    [nnz]            fp32 edge weights in layout order, or NULL (unweighted)
+ * r <= cogdl_hip_csr_spmm_sweep_group_rows().  Only f32 with k = 128 (512-byte rows); other shapes: COGDL_HIP_EUNSUPPORTED.
+ * cogdl_hip_csr_spmm_sweep_round_rows(k, dtype): how many rows the waves resident on the current device hold at once for this
+ * width (0: a width the kernel declines); more rows are walked as further groups by the same waves -- correct, less local.
+ * Tuning key 18 caps the rows of one round (tests). */
+COGDL_API int cogdl_hip_csr_spmm_sweep_group_rows(void);
+COGDL_API int64_t cogdl_hip_csr_spmm_sweep_round_rows(int64_t k, int dtype);
+COGDL_API int cogdl_hip_csr_spmm_sweep(const int32_t *goff, const int32_t *src, const void *w, const void *x, void *out,
+                                       int64_t m, int64_t n_src, int64_t n_groups, int r, int64_t k, int64_t nnz, int dtype,
+                                       void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * 64-bit CSR ("big CSR", ABI v7): graphs of 2^31 edges and more -- ogbn-papers100M as CogDL feeds it to GCN
