@@ -4,13 +4,19 @@ library's skip-gram operator -- what the reference's DeepWalk / Node2vec do thro
 
     deepwalk(graph_or_csr, dim, walk_length, walk_num, window, epochs)      -> float32 [N, dim]
     node2vec(graph_or_csr, dim, walk_length, walk_num, window, epochs, p, q) -> float32 [N, dim]
+    netsmf(graph_or_csr, dim, window, negative, rounds)                     -> float32 [N, dim]
 
 `graph_or_csr` is a cogdl Graph (its row_indptr / col_indices are used on the device they live on) or an
 (indptr, indices) pair of int64 tensors.  Each of the walk_num passes starts one walk at every node, in an order shuffled
 per pass (as the reference does); the passes' rows follow each other, which is the order the trainer consumes them in.
 Differences from the reference: the draws come from Philox, not from numpy's / gensim's generators; at a node without
 out-neighbours the walker stays (the reference ends the walk); node2vec ignores edge weights.
+
+netsmf is the matrix-factorisation member of the family (cogdl/models/emb/netsmf.py): path samples counted into a sparse
+matrix, the sparsifier's log transform, a randomized SVD -- all three from cogdl_amd/operators/netsmf.py, nothing trained.
 """
+import math
+
 import torch
 
 from .operators.sgns import skipgram
@@ -57,3 +63,27 @@ def node2vec(graph_or_csr, dim=128, walk_length=80, walk_num=40, window=5, epoch
     """node2vec: second-order walks with return parameter p and in-out parameter q, then skip-gram."""
     return _embed(lambda ip, ix, st, sd: node2vec_walk(ip, ix, st, walk_length, p=p, q=q, seed=sd), graph_or_csr, dim, walk_length,
                   walk_num, window, epochs, seed, negative, alpha, min_alpha, sample, workers)
+
+
+def netsmf(graph_or_csr, dim=128, window=10, negative=1, rounds=100, seed=None):
+    """NetSMF on a simple symmetric graph with unit weights -> float32 [N, dim] on the graph's device: U sqrt(S) of the
+    sparsifier's randomized SVD with the rows L2-normalised (netsmf.py:122-132).  `rounds` is the reference's num_round: a
+    round takes every undirected edge once in a random orientation, which is half a pass over the CSR entries, so
+    passes = ceil(rounds / 2).  A node without edges gets a zero row (as does any row whose U sqrt(S) is zero)."""
+    from .operators.netsmf import path_counts, randomized_svd, sparsifier
+
+    rounds, dim = int(rounds), int(dim)
+    if rounds < 1:
+        raise ValueError("rounds must be >= 1 (got %d)" % rounds)
+    indptr, indices = _csr(graph_or_csr)
+    n = indptr.numel() - 1
+    if not 1 <= dim <= n:
+        raise ValueError("dim must be in [1, N = %d] (got %d)" % (n, dim))
+    passes = math.ceil(rounds / 2)
+    seed = _seed(seed)
+    rowptr, col, count = path_counts(indptr, indices, window, passes, seed=seed)
+    m_rowptr, m_col, m_val = sparsifier(indptr, rowptr, col, count, window, passes, negative)
+    u, s = randomized_svd(m_rowptr, m_col, m_val, n, dim, seed=(seed + 1) & (2 ** 64 - 1))
+    emb = u * s.sqrt()
+    norm = emb.norm(dim=1, keepdim=True)
+    return torch.where(norm > 0, emb / norm.clamp_min(1e-30), torch.zeros_like(emb))

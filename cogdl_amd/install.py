@@ -40,7 +40,7 @@ _finder = None
 
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
             metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False, readout=False,
-            relational=False, genconv=False, disengcn=False, contrast=False):
+            relational=False, genconv=False, disengcn=False, contrast=False, netsmf=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -117,6 +117,14 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     the two [N, N] score matrices is kept; there is no HIP kernel behind it, GPU tensors run torch's kernels and say so once
     with a TorchRouteWarning).  batched_loss calls the rebound method and is served as it stands.  Inputs that are not 2-D
     float tensors of one width reach the reference's method.
+    netsmf=True rebinds NetSMF.forward in cogdl.models.emb.netsmf (opt-in: the draws are Philox's, not numpy's; num_round rounds
+    become ceil(num_round / 2) passes over the CSR entries, so an odd num_round is rounded up; a node without edges gets a zero
+    row where the reference divides by its degree) to cogdl_amd.netsmf_compat: the simple symmetric structure of edge_index is
+    built on the graph's device, the num_round * num_edge * window_size path samples come from the library's path sampler (HIP
+    kernel for a graph on the GPU, the OpenMP host twin otherwise) instead of an interpreted loop into a scipy lil_matrix, the
+    sparsifier and the randomized SVD run there too (cogdl_amd/operators/netsmf.py), with the same return value
+    (features_matrix as numpy [N, dim], or the dict with return_dict=True).  A graph whose edge weights are not all equal and
+    a graph without edges reach the reference's forward.
     linear=True additionally routes torch.nn.functional.linear -- i.e. the unchanged nn.Linear inside every CogDL
     layer -- through cogdl_amd.linear (hand-written MFMA weight gradient for full-graph shapes)."""
     global _finder
@@ -202,6 +210,12 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
         _import_target(contrast_compat._MODULE, "contrast")
         if not contrast_compat.install():
             raise _lib_error("install(contrast=True): GRACEModelWrapper.contrastive_loss could not be rebound")
+    if netsmf:
+        from . import netsmf_compat
+
+        _import_target(netsmf_compat._MODULE, "netsmf")
+        if not netsmf_compat.install():
+            raise _lib_error("install(netsmf=True): NetSMF.forward could not be rebound")
     su = sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):

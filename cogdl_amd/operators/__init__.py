@@ -22,6 +22,8 @@
     contrast.py      pair_lse, grace_loss (also exported here)         (GRACEModelWrapper.contrastive_loss,
                                                                         wrappers/model_wrapper/node_classification/grace_mw.py:64-77)
 
+    netsmf.py        path_pairs, path_counts, sparsifier, randomized_svd (also exported here)   (models/emb/netsmf.py)
+
     ops.py           scatter_add, op_aggr, s_*_e_sum / s_*_e_mean (fused HIP), s_*_e, s_*_t   (cogdl/operators/ops.py)
 
 Submodules are imported lazily: GPU modules load libcogdl_hip.so at import and raise if it
@@ -62,4 +64,8 @@ def __getattr__(name):
         from . import contrast
 
         return getattr(contrast, name)
+    if name in ("path_pairs", "path_counts", "sparsifier", "randomized_svd"):
+        from . import netsmf
+
+        return getattr(netsmf, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

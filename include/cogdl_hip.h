@@ -904,6 +904,33 @@ COGDL_API int cogdl_hip_node2vec_walk(const int64_t *indptr, const int64_t *indi
                             const int64_t *start, int64_t n_walkers, int64_t length, double p, double q, int max_trials,
                             uint64_t seed, int64_t *walks, int32_t *fallback_steps, int *flags, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * NetSMF path sampling on a GPU-resident CSR graph (csrc/netsmf.hip): int64 indptr[num_nodes + 1] / indices[num_edges], unit
+ * weights; result int32 out_row / out_col of window * n_samples entries each.
+ * Stream-ordered, one launch (plus one word fill), no host round trip, no atomics, no workspace; hipGraph-capturable.
+ * Replaces the interpreted loop of cogdl/models/emb/netsmf.py:134-159 (_path_sampling / _random_walk_matrix).  Host twin
+ * with identical results: cogdl_host_netsmf_sample (include/cogdl_host.h).  The law is csrc/netsmf_law.h's:
+ *   sample (s, r)  s in [first_sample, first_sample + n_samples), r in [1, window].  e = s mod num_edges; u = the row that
+ *                  holds entry e (empty rows are skipped), v = indices[e]; k uniform on 1 .. r; u takes k - 1 uniform
+ *                  steps, v takes r - k.  The pair is written at j = (r - 1) * n_samples + (s - first_sample).
+ *   One pass       s = 0 .. num_edges - 1 visits every entry once: on a simple symmetric graph `num_round` rounds of the
+ *                  reference (each undirected edge once, with a fair flip of its orientation) have the law of
+ *                  num_round / 2 passes.
+ *   Dead ends      at a node without out-neighbours the walker stays, as in cogdl_hip_random_walk.
+ *   Randomness     a pure function of (seed, s, r, step i) through Philox4x32-10 (csrc/walk_draw.h): independent of launch
+ *                  shape, of scheduling, and of how a range of samples is cut into calls.
+ *   flags          DEVICE int, zeroed by the call: bit 1 a neighbour id outside [0, num_nodes), bit 2 a row of indptr that
+ *                  is not a range inside [0, num_edges] or does not hold the entry it should.  Such a sample writes
+ *                  (-1, -1); nothing is read out of bounds.  Non-zero marks an invalid result; when both conditions occur
+ *                  in one call a bit may be missing, the word is never zero then.
+ *   n_samples = 0 is valid (the flags word is still zeroed).  window outside [1, 256], num_edges = 0 or num_nodes = 0 with
+ *   n_samples > 0, a negative size: COGDL_HIP_EINVAL.  num_nodes >= 2^31 (pairs are int32) or n_samples > 2^53:
+ *   COGDL_HIP_ERANGE.  Offsets are 64-bit throughout (num_edges and window * n_samples >= 2^31 are fine).
+ * ------------------------------------------------------------------------------------- */
+COGDL_API int cogdl_hip_netsmf_sample(const int64_t *indptr, const int64_t *indices, int64_t num_nodes, int64_t num_edges,
+                            int64_t first_sample, int64_t n_samples, int window, uint64_t seed, int32_t *out_row,
+                            int32_t *out_col, int *flags, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Top-k personalised PageRank by forward push (csrc/ppr.hip), replacing the numba / interpreted loop of
  * cogdl/utils/ppr_utils.py:8-48.  int64 indptr[num_nodes + 1] / indices[num_edges] on the device, deg[u] =

@@ -102,6 +102,16 @@ COGDL_HOST_API int cogdl_host_node2vec_walk(const int64_t *indptr, const int64_t
                                             double p, double q, int max_trials, uint64_t seed, int64_t *walks,
                                             int32_t *fallback_steps, int *flags);
 
+/* NetSMF path sampling, the host twin of cogdl_hip_netsmf_sample (include/cogdl_hip.h, where the contract is spelled out):
+ * same arguments minus the stream, and for equal inputs and seed EXACTLY the arrays the GPU returns -- both run
+ * csrc/netsmf_law.h.  out_row / out_col: int32[window * n_samples], sample (s, r) at (r - 1) * n_samples + (s - first_sample).
+ * OpenMP over the output positions; the result does not depend on the number of threads.  *flags (host int): bit 1 a
+ * neighbour id outside [0, num_nodes), bit 2 a malformed row of indptr; such samples are (-1, -1), nothing is read out of
+ * bounds.  Bad sizes: COGDL_HOST_EINVAL; num_nodes >= 2^31 or n_samples > 2^53: COGDL_HOST_ERANGE. */
+COGDL_HOST_API int cogdl_host_netsmf_sample(const int64_t *indptr, const int64_t *indices, int64_t num_nodes,
+                                            int64_t num_edges, int64_t first_sample, int64_t n_samples, int window,
+                                            uint64_t seed, int32_t *out_row, int32_t *out_col, int *flags);
+
 /* Top-k personalised PageRank by forward push; the host twin of cogdl_hip_ppr_topk (include/cogdl_hip.h, where the contract
  * is spelled out): same arguments minus workspace and stream, and for equal inputs EXACTLY the arrays the GPU returns --
  * both run the fixed-point arithmetic of csrc/ppr_fixed.h in the same synchronous rounds.  OpenMP over the sources; the
