@@ -107,8 +107,10 @@ struct SpmmOp {
                                           int) const {
         float xv[VEC];
         if constexpr (sizeof(T) == 2 && !EPI && sizeof(Raw) % 4 == 0) {
-            // 16-bit features: no bit-exact contract (products and sums are fp32, rounded once on store; parity is a
-            // tolerance).  The masked slot is zeroed on its RAW words (VEC / 2 selects instead of VEC) and the update is a
+            // 16-bit features: no bit-exact contract for WEIGHTED sums (products and sums are fp32, rounded once on store;
+            // parity is a tolerance: half an ulp of the output plus the fp32 summation error, tests/_halfprec.py).  Unweighted
+            // rows only add, here as in the branch below: up to the exact-row bound they equal the fp32 loop's result rounded
+            // once (include/cogdl_hip.h).  The masked slot is zeroed on its RAW words (VEC / 2 selects instead of VEC) and the update is a
             // fused multiply-add (one packed instruction per two columns instead of two): on hub-heavy graphs this kernel
             // is bound by VALU issue, not by bytes (round 6, profiles/r06_sq_reddit.txt).
             union { Raw raw; uint32_t w[sizeof(Raw) / 4]; } m;

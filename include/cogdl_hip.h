@@ -95,6 +95,10 @@ COGDL_API int cogdl_hip_probe_copy_stream(const void *src, void *dst, size_t byt
  * f32: each output element is accumulated sequentially in CSR edge order with a separate
  * fp32 multiply and add -- bit-identical to the reference CPU path as CogDL builds it.
  * f16/bf16: val has the dtype of x; products and sums are fp32, rounded once on store.
+ * Weighted 16-bit sums are fp32 fused multiply-adds at vector widths of at least 2 and a rounded multiply followed by a
+ * rounded add at width 1 (odd k, or x / out not 4-byte aligned): results can therefore differ in the last place with the
+ * parity of k and with pointer alignment.  Unweighted 16-bit rows of at most cogdl_hip_exact_row_edges(nnz) edges equal the
+ * fp32 result (the reference loop on the 16-bit inputs) rounded once, whatever the width or alignment.
  * x: [n_src, k], out: [m, k]; rowptr: [m+1]; colind/val: [nnz], nnz == rowptr[m].
  * workspace (optional, device, 256-B aligned, >= cogdl_hip_csr_spmm_workspace_bytes(nnz, k, dtype)):
  * enables the chunk-parallel treatment of rows longer than cogdl_hip_long_row_threshold(nnz)
@@ -318,6 +322,10 @@ COGDL_API int cogdl_hip_edge_softmax_bwd(const int32_t *rowptr, const void *soft
  * mhspmm:  out[v,h,:] = sum_e att[e,h] * feat[colind[e],h,:]     feat [n_src,H,F]
  * Replaces mhspmm.mhspmm (operators/spmm/multiheadSpmm.cpp, multiheadSpmm.cu:6-77).
  * att is always f32; feat/out have `dtype` (f32: sequential fp32 mul+add per element).
+ * f16/bf16 feat: fp32 arithmetic, rounded once on store.  Weighted 16-bit sums are fp32 fused multiply-adds at vector widths
+ * of at least 2 and multiply-then-add at width 1 (odd F, or feat / out not 4-byte aligned): results can therefore differ in
+ * the last place with the parity of F and with pointer alignment.  (Unweighted 16-bit rows up to the exact-row bound equal
+ * the fp32 result rounded once: csr_spmm with val == NULL; mhspmm always has weights.)
  * workspace: cogdl_hip_mhspmm_workspace_bytes(nnz, H, F, dtype) (mhsddmm needs none).
  * mhsddmm: out[e,h] = < grad[row(e),h,:], feat[colind[e],h,:] >
  * Replaces mhsddmm.mhsddmm (operators/spmm/multiheadSddmm.cu:6-113).
