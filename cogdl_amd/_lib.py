@@ -36,6 +36,8 @@ HIP_SIGNATURES = {
     "cogdl_hip_csr_spmm_sweep_group_rows": ([], _i32),
     "cogdl_hip_csr_spmm_sweep_round_rows": ([_i64, _i32], _i64),
     "cogdl_hip_csr_spmm_sweep": ([_vp] * 5 + [_i64, _i64, _i64, _i32, _i64, _i64, _i32, _vp], _i32),
+    "cogdl_hip_csr_spmm_sweep_guarded": ([_vp] * 5 + [_i64, _i64, _i64, _i32, _i64, _i64, _i32, _vp, _u64, _i32, _vp], _i32),
+    "cogdl_hip_csr_spmm_guarded": ([_vp] * 5 + [_i64, _i64, _i64, _i32, _vp, _u64, _i32, _vp, _sz, _vp], _i32),
     "cogdl_hip_gat_fwd_xcd_workspace_bytes": ([_i64, _i64, _i64, _i32], _sz),
     "cogdl_hip_gat_fwd_xcd": ([_vp] * 4 + [_f32, _f32, _u64] + [_vp] * 3 + [_i64, _i64, _i64, _i32, _vp, _sz, _vp], _i32),
     "cogdl_hip_gat_bwd_xcd_workspace_bytes": ([_i64, _i64, _i64, _i64, _i64, _i32], _sz),
@@ -93,6 +95,7 @@ HIP_SIGNATURES = {
     "cogdl_hip_edge_dropout_mask": ([_i64, _i64, _f32, _u64, _vp, _vp], _i32),
     "cogdl_hip_edge_dropout_mask_host": ([_i64, _i64, _f32, _u64, _vp], _i32),
     "cogdl_hip_csr_fingerprint": ([_vp, _vp, _i64, _i64, _vp, _vp], _i32),
+    "cogdl_hip_csr_fingerprint_dev": ([_vp, _vp, _i64, _i64, _vp, _vp, _vp], _i32),
     "cogdl_hip_linear_fwd_f32": ([_vp] * 4 + [_i64, _i64, _i64, _i32, _vp], _i32),
     "cogdl_hip_linear_fwd_bf16": ([_vp, _i32, _vp, _i32, _vp, _vp, _i64, _i64, _i64, _i32, _vp], _i32),
     "cogdl_hip_head_projection_fwd": ([_vp, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp], _i32),

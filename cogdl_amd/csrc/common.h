@@ -162,4 +162,27 @@ __device__ __forceinline__ float group_max(float v) {
     return v;
 }
 
+// A launch that runs only if the structure hash the stream has just computed is (or is not) a given key.  `parts`: the 256
+// partials of csr_fingerprint_kernel in DEVICE memory (cogdl_hip_csr_fingerprint_dev, enqueued on the same stream in front of
+// the guarded launch: ordered by the stream, 2 KB, an L2 hit); the key is their sum modulo 2^64 -- integer, so every wave may
+// sum them in its own order.  Every wave decides for itself in its prologue: no flag, no atomic, nothing is written.
+struct HashGuard {
+    const unsigned long long *parts;  // [256], 16-byte aligned
+    unsigned long long expect;
+    int run_if_equal;  // 1: run on a match, stand down otherwise; 0: the other way round
+};
+
+__device__ __forceinline__ bool guard_runs(const HashGuard &g) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const ulonglong2 *p = reinterpret_cast<const ulonglong2 *>(g.parts) + 2 * lane;  // four partials per lane
+    const ulonglong2 a = p[0], b = p[1];
+    unsigned long long acc = a.x + a.y + b.x + b.y;
+#pragma unroll
+    for (int s = kWave / 2; s > 0; s >>= 1) {
+        const uint32_t lo = __shfl_xor((uint32_t)acc, s, kWave), hi = __shfl_xor((uint32_t)(acc >> 32), s, kWave);
+        acc += ((unsigned long long)hi << 32) | lo;
+    }
+    return (acc == g.expect) == (g.run_if_equal != 0);
+}
+
 }  // namespace cogdl

@@ -98,6 +98,21 @@ struct MinWaves<Op, std::void_t<decltype(Op::kMinWaves)>> {
     static constexpr int value = Op::kMinWaves;
 };
 
+// An operator wrapped in Guarded<> carries a HashGuard (common.h): its main kernel AND its combine kernel stand down, first
+// thing, unless the guard says run -- compiled into that instantiation only, every other kernel keeps its code.  A launch that
+// stands down writes nothing, so nothing of it may be read either: the combine kernel asks the guard before it looks at found[].
+template <class Op, class = void>
+struct IsGuarded : std::false_type {};
+template <class Op>
+struct IsGuarded<Op, std::void_t<decltype(Op::kGuarded)>> : std::true_type {};
+template <class Base>
+struct Guarded : Base {
+    static constexpr bool kGuarded = true;
+    HashGuard guard;
+    unsigned row_grid;  // row-block workgroups of the FULL grid (the launch itself has at most kGuardedRowGrid: see the main kernel)
+};
+constexpr unsigned kGuardedRowGrid = 2048;  // 256 CUs x 8 workgroups of 4 waves: what is resident at once (a multiple of 8)
+
 // Threshold above which a row is split.  The sequential time of a row of T edges (~T/UNROLL gather round trips of
 // ~1 us) must stay a small fraction of the launch; small graphs need a low threshold, large ones amortise more.
 inline int pick_long_thresh(int64_t nnz) {
@@ -502,21 +517,13 @@ __device__ __forceinline__ bool deal_rows_by_length(int slot, bool leader, bool 
 // tuning key 2: 1 = keep the natural row -> lane-group assignment inside a workgroup (experiments)
 __device__ __forceinline__ bool g_sort_rows(const RowSched &s) { return s.sort_rows != 0; }
 
-// Grid: [ n_long_blocks long-row workgroups | row-block workgroups ]  x  column tiles.  The long-row workgroups come
-// first so that the (critical-path) hub rows start at once; they cost a graph without hub rows ~17 dependent
-// L2-resident loads in <= 1024 workgroups, overlapped with the row blocks.
+// One row block: workgroup `bid` of the row-block part of the grid (before the XCD remap) reduces its GPB rows.
 template <class Op>
-__global__ __launch_bounds__(256, MinWaves<Op>::value) void rowreduce_main_kernel(const Op op, const RowSched s) {
-    __shared__ float op_lds[Op::kLds > 0 ? 256 * Op::kLds : 1];  // one buffer for both kinds of workgroup
-    if (blockIdx.x < s.lr.n_long_blocks) {
-        if (s.debug != 2) rowreduce_long_block<Op>(op, s, op_lds);
-        return;
-    }
-    if (s.debug == 1) return;
+__device__ __forceinline__ void rowreduce_row_block(const Op &op, const RowSched &s, unsigned bid, float *op_lds) {
     constexpr int LPR = Op::LPR;
     constexpr int RPW = kWave / LPR;  // row groups per wave
     constexpr int GPB = RPW * 4;      // row groups per 256-thread workgroup
-    const int64_t rb = xcd_remap(blockIdx.x - s.lr.n_long_blocks, s.rowblocks);
+    const int64_t rb = xcd_remap(bid, s.rowblocks);
     if (rb < 0) return;
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x >> 6;
@@ -565,6 +572,33 @@ __global__ __launch_bounds__(256, MinWaves<Op>::value) void rowreduce_main_kerne
     op.row_end(ctx, st, row, ok);
 }
 
+// Grid: [ n_long_blocks long-row workgroups | row-block workgroups ]  x  column tiles.  The long-row workgroups come
+// first so that the (critical-path) hub rows start at once; they cost a graph without hub rows ~17 dependent
+// L2-resident loads in <= 1024 workgroups, overlapped with the row blocks.
+// A guarded launch (Guarded<Op>) has at most kGuardedRowGrid row-block workgroups, each walking the row blocks bid, bid +
+// stride, ... of the full grid (op.row_grid of them): a launch that stands down -- the usual case, it is the fallback of a
+// speculation -- then costs 2 k workgroups that leave at once instead of one per four rows (arxiv-sized graph: 42 k, measured
+// 26 us for nothing).  Whole-wave rows only: the walk has no barrier, a wave may leave a row block on its own.
+template <class Op>
+__global__ __launch_bounds__(256, MinWaves<Op>::value) void rowreduce_main_kernel(const Op op, const RowSched s) {
+    __shared__ float op_lds[Op::kLds > 0 ? 256 * Op::kLds : 1];  // one buffer for both kinds of workgroup
+    if constexpr (IsGuarded<Op>::value) {
+        if (!guard_runs(op.guard)) return;  // (the same answer in every wave of the grid: no barrier is left waiting)
+    }
+    if (blockIdx.x < s.lr.n_long_blocks) {
+        if (s.debug != 2) rowreduce_long_block<Op>(op, s, op_lds);
+        return;
+    }
+    if (s.debug == 1) return;
+    if constexpr (IsGuarded<Op>::value) {
+        static_assert(Op::LPR == kWave, "guarded launches: whole-wave rows");
+        const unsigned stride = gridDim.x - s.lr.n_long_blocks;  // (a multiple of 8: bid % 8 stays the workgroup's XCD)
+        for (unsigned bid = blockIdx.x - s.lr.n_long_blocks; bid < op.row_grid; bid += stride) rowreduce_row_block<Op>(op, s, bid, op_lds);
+    } else {
+        rowreduce_row_block<Op>(op, s, blockIdx.x - s.lr.n_long_blocks, op_lds);
+    }
+}
+
 // For every long row merge its piece records in chunk order and finish the row.  The row is combined by the lane
 // group that finds it at its FIRST full chunk (the row's head piece, if any, sits in slot 1 of the chunk before).
 template <class Op>
@@ -577,6 +611,9 @@ __global__ __launch_bounds__(256) void rowreduce_combine_kernel(const Op op, con
     const LongRows &lr = s.lr;
     const int64_t c_begin = (int64_t)blockIdx.x * lr.chunks_per_block;
     if (c_begin >= lr.n_chunks) return;
+    if constexpr (IsGuarded<Op>::value) {
+        if (!guard_runs(op.guard)) return;  // (the main kernel stood down too: found[] and the records are not written)
+    }
     // A row combined here owns the first edge of one of this run's chunks, so the long-row workgroup of the same run
     // met it (slot 0): found[] == 0 means nothing to do -- one load instead of a search.
     if (lr.found && lr.found[blockIdx.x] == 0) return;
@@ -858,7 +895,14 @@ static int launch_rowreduce(const Op &op, const int32_t *rowptr, const int32_t *
     }
     if (!grid_fits(s.rowblocks, s.lr.n_long_blocks)) return COGDL_HIP_ERANGE;
     dim3 grid(s.lr.n_long_blocks + xcd_grid(s.rowblocks), (unsigned)tiles);
-    hipLaunchKernelGGL((rowreduce_main_kernel<Op>), grid, dim3(256), 0, stream, op, s);
+    if constexpr (IsGuarded<Op>::value) {
+        Op gop = op;
+        gop.row_grid = xcd_grid(s.rowblocks);
+        grid.x = s.lr.n_long_blocks + std::min(gop.row_grid, kGuardedRowGrid);
+        hipLaunchKernelGGL((rowreduce_main_kernel<Op>), grid, dim3(256), 0, stream, gop, s);
+    } else {
+        hipLaunchKernelGGL((rowreduce_main_kernel<Op>), grid, dim3(256), 0, stream, op, s);
+    }
     if constexpr (Op::kReduce) {
         if (s.lr.n_long_blocks > 0)
             hipLaunchKernelGGL((rowreduce_combine_kernel<Op>), dim3(s.lr.n_long_blocks, (unsigned)tiles), dim3(256), 0,

@@ -1,5 +1,5 @@
-// rowsweep.h -- csr_spmm over a SWEEP layout of a column-sorted structure (the stable transpose of the backward pass): every
-// wave owns a group of consecutive rows and walks the edges of ALL of them merged in ascending order of the gathered row.
+// rowsweep.h -- csr_spmm over a SWEEP layout: every wave owns a group of consecutive rows and walks the edges of ALL of them
+// merged in an order in which the gathered row (almost) only ascends.
 //
 // Why.  The fp32 F = 128 launch of the arxiv-sized graph gathers 512-byte rows of an 87 MB table uniformly at random: an XCD's
 // 4 MiB L2 holds 4.6 % of it, the launch runs at the fabric rate.  When every wave of the chip walks the table top to bottom
@@ -7,9 +7,19 @@
 // edges of the XCD's rows is fetched across the fabric once.  Nothing enforces the pace -- no wave waits for another, there is
 // no atomic and no flag: correctness never depends on it, only the hit rate does.
 //
-// What stays the same.  Inside every row of a stable transpose the gathered rows ascend, so the merged walk visits the edges
-// of each row in exactly the row's own order: acc = acc + w * x, separately rounded (-ffp-contract=off), bit-identical to
-// rowreduce_main_kernel<SpmmOp<float, 2, 64, 8, ...>> on the same structure.
+// What stays the same.  The merged walk is a STABLE sort of a group's edges on a key that never decreases inside a row, so it
+// visits the edges of each row in exactly the row's own order: acc = acc + w * x, separately rounded (-ffp-contract=off),
+// bit-identical to rowreduce_main_kernel<SpmmOp<float, 2, 64, 8, ...>> on the same structure.  Backward: the rows of a stable
+// transpose list their gathered rows ascending, the key is the gathered row itself.  Forward: the caller's rows need not be
+// column-sorted; the key is the running maximum of the column inside the row (cogdl_amd/sweepplan.py: build_forward) -- an
+// edge behind its row's running maximum is walked where that maximum is, i.e. gathered out of table order: it costs hit rate
+// (the policy asks for few of them), never bits.
+//
+// Guarded launches (rowreduce_sweep_guarded_kernel, cogdl_hip_csr_spmm_sweep_guarded).  The forward's layout belongs to a
+// structure seen EARLIER; whether the call at hand passes that structure is known to the device only (the call's hash is
+// still in flight to the host).  The guarded kernel compares the hash the stream has just computed with the layout's key in
+// every wave's prologue (common.h: HashGuard) and walks the layout on a match; otherwise it leaves at once and the ordinary
+// launch, guarded the other way round, does the work.  The walk itself is the same code.
 //
 // Layout (cogdl_amd/sweepplan.py), group g = rows [g * r, min((g + 1) * r, m)), r <= kSweepRows:
 //   goff [n_groups + 1]   edge offsets of the groups
@@ -61,8 +71,9 @@ __device__ __forceinline__ void sweep_fold(SweepF32x32 &lo0, SweepF32x32 &lo1, f
 
 // One wave per row group, four waves per workgroup; groups beyond one round of the grid are walked by the same waves,
 // grid-stride (correct, only less local).  Rows of 128 fp32 columns: one float2 per lane.
+// (The body of both kernels below: the unguarded one is this and nothing else.)
 template <bool WEIGHTED>
-__global__ __launch_bounds__(256, 4) void rowreduce_sweep_kernel(const SweepArgs a) {
+__device__ __forceinline__ void sweep_walk(const SweepArgs &a) {
     constexpr int UNROLL = kSweepUnroll;
     const int lane = threadIdx.x & (kWave - 1);
     const uint32_t lane_off = (uint32_t)lane * (uint32_t)sizeof(float2);
@@ -129,6 +140,18 @@ __global__ __launch_bounds__(256, 4) void rowreduce_sweep_kernel(const SweepArgs
             }
         }
     }
+}
+
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256, 4) void rowreduce_sweep_kernel(const SweepArgs a) {
+    sweep_walk<WEIGHTED>(a);
+}
+
+// The same walk, taken only if the guard says so (see the header comment); a wave that stands down has written nothing.
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256, 4) void rowreduce_sweep_guarded_kernel(const SweepArgs a, const HashGuard guard) {
+    if (!guard_runs(guard)) return;
+    sweep_walk<WEIGHTED>(a);
 }
 
 // Waves of one round on the current device (CU count x waves that fit), capped by tuning key 18 (tests: rows per round).

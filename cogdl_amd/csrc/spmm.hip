@@ -238,6 +238,58 @@ extern "C" int cogdl_hip_csr_spmm_sweep(const int32_t *goff, const int32_t *src,
     return launch_status();
 }
 
+// ---- guarded launches: the forward pass over a layout cached for a structure seen earlier (rowsweep.h, common.h: HashGuard) ----
+static_assert(COGDL_HIP_FINGERPRINT_PARTS == 4 * kWave, "guard_runs sums four partials per lane");
+
+static int make_guard(HashGuard &g, const uint64_t *parts, uint64_t expect, int run_if_equal) {
+    if (!parts || (run_if_equal != 0 && run_if_equal != 1)) return COGDL_HIP_EINVAL;
+    if (!aligned_to(parts, 16)) return COGDL_HIP_EALIGN;
+    g = HashGuard{(const unsigned long long *)parts, (unsigned long long)expect, run_if_equal};
+    return COGDL_HIP_OK;
+}
+
+extern "C" int cogdl_hip_csr_spmm_sweep_guarded(const int32_t *goff, const int32_t *src, const void *w, const void *x, void *out,
+                                                int64_t m, int64_t n_src, int64_t n_groups, int r, int64_t k, int64_t nnz, int dtype,
+                                                const uint64_t *parts, uint64_t expect, int run_if_equal, void *stream) {
+    if (m < 0 || n_groups < 0 || nnz < 0 || r < 1 || r > kSweepRows) return COGDL_HIP_EINVAL;
+    if (dtype != COGDL_HIP_F32 || k != 2 * kWave) return COGDL_HIP_EUNSUPPORTED;
+    HashGuard guard;
+    int rc = make_guard(guard, parts, expect, run_if_equal);
+    if (rc != COGDL_HIP_OK) return rc;
+    if (m == 0) return COGDL_HIP_OK;
+    if (n_groups != (m + r - 1) / r) return COGDL_HIP_EINVAL;
+    if (!goff || !x || !out || (nnz > 0 && !src)) return COGDL_HIP_EINVAL;
+    if (nnz > COGDL_HIP_SEGMENT_MAX_EDGES) return COGDL_HIP_ERANGE;
+    if (!aligned_to(x, sizeof(float2)) || !aligned_to(out, sizeof(float2))) return COGDL_HIP_EALIGN;
+    if (n_src <= 0 || n_src > (1 << 23)) return COGDL_HIP_EUNSUPPORTED;  // (24-bit rows, 32-bit byte offsets into x)
+    const int64_t waves = sweep_round_waves();
+    if (waves <= 0) {
+        g_last_hip_error = (int)hipGetLastError();
+        return COGDL_HIP_ELAUNCH;
+    }
+    SweepArgs a{goff, (const uint32_t *)src, (const float *)w, (const float *)x, (float *)out, m, n_groups, r, (uint32_t)(k * sizeof(float))};
+    const unsigned blocks = (unsigned)((std::min(waves, n_groups) + 3) / 4);
+    if (w) hipLaunchKernelGGL((rowreduce_sweep_guarded_kernel<true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, guard);
+    else hipLaunchKernelGGL((rowreduce_sweep_guarded_kernel<false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, guard);
+    return launch_status();
+}
+
+extern "C" int cogdl_hip_csr_spmm_guarded(const int32_t *rowptr, const int32_t *colind, const void *val, const void *x, void *out,
+                                          int64_t m, int64_t k, int64_t nnz, int dtype, const uint64_t *parts, uint64_t expect,
+                                          int run_if_equal, void *workspace, size_t workspace_bytes, void *stream) {
+    int rc = check_args(rowptr, x, out, m, k, nnz);
+    if (rc != COGDL_HIP_OK) return rc;
+    if (dtype != COGDL_HIP_F32 || k != 2 * kWave) return COGDL_HIP_EUNSUPPORTED;
+    HashGuard guard;
+    rc = make_guard(guard, parts, expect, run_if_equal);
+    if (rc != COGDL_HIP_OK || m == 0) return rc;
+    if (!aligned_to(x, sizeof(float)) || !aligned_to(out, sizeof(float))) return COGDL_HIP_EALIGN;
+    SpmmArgs<float> a{rowptr, colind, (const float *)val, nullptr, (const float *)x, (float *)out, m, nnz, (int)k, (int)k, 0, nullptr, {}};
+    a.guard = &guard;
+    // (operands the geometry rule gives other lanes than the headline's -- 4-byte aligned tables -- come back EUNSUPPORTED)
+    return val ? spmm_auto<float, 1>(a, workspace, workspace_bytes, (hipStream_t)stream) : spmm_auto<float, 0>(a, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 // ---- 64-bit CSR: one launch per row segment (bigcsr.hip) ---------------------------------------------------------------
 extern "C" size_t cogdl_hip_csr_spmm_i64_workspace_bytes(const cogdl_hip_segments *seg, int64_t k, int dtype) {
     if (segments_valid(seg) != COGDL_HIP_OK) return 0;

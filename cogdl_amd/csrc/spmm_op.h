@@ -182,6 +182,7 @@ struct SpmmArgs {
     SpmmEpilogue epi;
     const cogdl_hip_vrows *vr = nullptr;  // XCD-partitioned plan (rowreduce.h): rowptr / colind are then unused
     const int32_t *row_order = nullptr;   // ordinary launch: the row blocks' schedule (rowreduce.h: RowSched::order)
+    const HashGuard *guard = nullptr;     // ordinary launch: run only if the guard says so (rowreduce.h: Guarded; fp32 F = 128 only)
 };
 
 template <typename T, int VEC, int LPR, int UNROLL, int WMODE, bool EXACT, bool EPI = false>
@@ -201,6 +202,12 @@ static int launch_spmm(const SpmmArgs<T> &a, void *ws, size_t wsb, hipStream_t s
             } else return COGDL_HIP_EUNSUPPORTED;
         }
         SpmmOp<T, VEC, LPR, UNROLL, WMODE, EXACT, EPI> op{a.val, a.att, a.x, a.out, a.k, a.fdim, a.acc_mode, a.eid, a.epi};
+        if (a.guard) {  // the one geometry a guarded launch exists for: the headline's (whole-wave rows of 8-byte lanes)
+            if constexpr (std::is_same_v<T, float> && VEC == 2 && LPR == kWave && UNROLL == kDefaultUnroll && WMODE != 2 && EXACT && !EPI) {
+                Guarded<decltype(op)> gop{op, *a.guard};
+                return launch_rowreduce(gop, a.rowptr, a.colind, a.m, a.nnz, tiles, ws, wsb, s, a.row_order);
+            } else return COGDL_HIP_EUNSUPPORTED;
+        }
         return launch_rowreduce(op, a.rowptr, a.colind, a.m, a.nnz, tiles, ws, wsb, s, a.row_order);
     }
 }

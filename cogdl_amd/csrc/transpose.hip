@@ -96,9 +96,9 @@ __device__ __forceinline__ uint64_t hash_stream(const int32_t *__restrict__ p, i
 
 // One partial per workgroup, written with a plain store (the target may be host-mapped pinned memory): no memset,
 // no atomics, no device-to-host copy behind it.  The fingerprint is the sum of the partials modulo 2^64.
-__global__ __launch_bounds__(256) void csr_fingerprint_kernel(const int32_t *__restrict__ rowptr,
-                                                              const int32_t *__restrict__ colind, int64_t m,
-                                                              int64_t nnz, unsigned long long *out) {
+// (Returns the workgroup's partial in thread 0.)
+__device__ __forceinline__ unsigned long long fingerprint_partial(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ colind,
+                                                                  int64_t m, int64_t nnz) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
     const int64_t tid4 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     uint64_t acc = hash_stream(rowptr, m + 1, tid4, stride, 0xa5a5a5a5a5a5a5a5ull) + hash_stream(colind, nnz, tid4, stride, 0);
@@ -111,7 +111,27 @@ __global__ __launch_bounds__(256) void csr_fingerprint_kernel(const int32_t *__r
     __shared__ unsigned long long part[4];
     if ((threadIdx.x & (kWave - 1)) == 0) part[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) out[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+    return part[0] + part[1] + part[2] + part[3];
+}
+
+__global__ __launch_bounds__(256) void csr_fingerprint_kernel(const int32_t *__restrict__ rowptr,
+                                                              const int32_t *__restrict__ colind, int64_t m,
+                                                              int64_t nnz, unsigned long long *out) {
+    const unsigned long long sum = fingerprint_partial(rowptr, colind, m, nnz);
+    if (threadIdx.x == 0) out[blockIdx.x] = sum;
+}
+
+// The same partials to TWO places: `out` (pinned host memory, for the plan cache's key) and `dev` (device memory, for the
+// launches behind this one on the stream that compare the hash themselves: common.h: HashGuard).  Only a call that speculates
+// on a cached layout pays the second store.
+__global__ __launch_bounds__(256) void csr_fingerprint_dev_kernel(const int32_t *__restrict__ rowptr,
+                                                                  const int32_t *__restrict__ colind, int64_t m,
+                                                                  int64_t nnz, unsigned long long *out, unsigned long long *dev) {
+    const unsigned long long sum = fingerprint_partial(rowptr, colind, m, nnz);
+    if (threadIdx.x == 0) {
+        out[blockIdx.x] = sum;
+        dev[blockIdx.x] = sum;
+    }
 }
 
 }  // namespace cogdl
@@ -205,6 +225,14 @@ extern "C" int cogdl_hip_csr_fingerprint(const int32_t *rowptr, const int32_t *c
     if (m < 0 || nnz < 0 || !rowptr || !out_parts) return COGDL_HIP_EINVAL;
     hipLaunchKernelGGL(csr_fingerprint_kernel, dim3(COGDL_HIP_FINGERPRINT_PARTS), dim3(256), 0, (hipStream_t)stream,
                        rowptr, colind, m, nnz, (unsigned long long *)out_parts);
+    return launch_status();
+}
+
+extern "C" int cogdl_hip_csr_fingerprint_dev(const int32_t *rowptr, const int32_t *colind, int64_t m, int64_t nnz,
+                                             uint64_t *out_parts, uint64_t *dev_parts, void *stream) {
+    if (m < 0 || nnz < 0 || !rowptr || !out_parts || !dev_parts) return COGDL_HIP_EINVAL;
+    hipLaunchKernelGGL(csr_fingerprint_dev_kernel, dim3(COGDL_HIP_FINGERPRINT_PARTS), dim3(256), 0, (hipStream_t)stream,
+                       rowptr, colind, m, nnz, (unsigned long long *)out_parts, (unsigned long long *)dev_parts);
     return launch_status();
 }
 

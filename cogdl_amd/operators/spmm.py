@@ -175,6 +175,53 @@ def csr_spmm_sweep_raw(csc, val, x):
     return out
 
 
+def csr_spmm_sweep_forward_raw(sp, parts, rowptr, colind, val, x):
+    """A x for a call that speculates on `sp`, the cached forward sweep layout (sweepplan.build_forward) of a structure seen
+    before: TWO guarded launches on the current stream writing the same `out` (cogdl_hip_csr_spmm_sweep_guarded "run if the
+    hash in `parts` is sp.hash", cogdl_hip_csr_spmm_guarded "run if it is not").  parts: the device partials of THIS call's
+    structure hash (plan.Fingerprint.dev), enqueued on the same stream.  Whichever launch runs gives csr_spmm_raw's bits; no
+    host synchronisation.  `val` in the caller's CSR edge order or None; fp32, 128 columns."""
+    from .. import sweepplan
+
+    dev = _lib.require_cuda(rowptr, colind, val, x, parts)
+    _check_csr(rowptr, colind, x)
+    m, k, nnz = rowptr.numel() - 1, x.shape[1], colind.numel()
+    if x.dtype != torch.float32 or (sp.n_rows, sp.nnz, sp.n_src) != (m, nnz, x.shape[0]) or sp.hash is None:
+        raise _lib.BackendError("csr_spmm_sweep_forward: a float32 [%d, k] operand and a layout of %d rows / %d edges with its "
+                                "structure's hash are needed" % (sp.n_src, m, nnz))
+    if parts.dtype != torch.int64 or parts.numel() != _plan.FINGERPRINT_PARTS or not parts.is_contiguous():
+        raise _lib.BackendError("csr_spmm_sweep_forward: the hash partials must be a contiguous int64 [%d] tensor" % _plan.FINGERPRINT_PARTS)
+    x, rowptr, colind = x.contiguous(), rowptr.contiguous(), colind.contiguous()
+    val_p = None
+    if val is not None:
+        if val.numel() != nnz:
+            raise _lib.BackendError("csr_data has %d entries for %d edges" % (val.numel(), nnz))
+        val = val.contiguous() if val.dtype == x.dtype else val.to(x.dtype)
+        val_p = sweepplan.forward_values(sp, val)
+    out = torch.empty((m, k), dtype=x.dtype, device=dev)
+    lib = _lib.hip()
+    code = _lib.DTYPE_CODE[x.dtype]
+    ws, ws_bytes = _lib.workspace("cogdl_hip_csr_spmm_workspace_bytes", dev, nnz, k, code)
+    with _lib.on_device(dev):
+        pair = None
+        if KERNEL_EVENTS is not None:
+            pair = (KERNEL_EVENTS.take() if hasattr(KERNEL_EVENTS, "take")
+                    else (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+        if pair is not None:
+            pair[0].record()
+        stream = _lib.stream_of(x)
+        rc = lib.cogdl_hip_csr_spmm_sweep_guarded(_lib.ptr(sp.goff), _lib.ptr(sp.src), _lib.ptr(val_p), _lib.ptr(x), _lib.ptr(out), m,
+                                                  sp.n_src, sp.n_groups, sp.r, k, nnz, code, _lib.ptr(parts), sp.hash, 1, stream)
+        if rc == 0:
+            rc = lib.cogdl_hip_csr_spmm_guarded(_lib.ptr(rowptr), _lib.ptr(colind), _lib.ptr(val), _lib.ptr(x), _lib.ptr(out), m, k,
+                                                nnz, code, _lib.ptr(parts), sp.hash, 0, _lib.ptr(ws), ws_bytes, stream)
+        if pair is not None:
+            pair[1].record()
+            KERNEL_EVENTS.append(pair)
+    _lib.check(rc, "csr_spmm_sweep_forward")
+    return out
+
+
 def csr_sddmm_raw(rowptr, colind, d1, d2):
     """out[e] = <d1[row(e)], d2[col[e]]>  (fp32)."""
     dev = _lib.require_cuda(rowptr, colind, d1, d2)
@@ -206,8 +253,13 @@ class SPMMFunction(torch.autograd.Function):
         else:
             ctx.fp = _plan.known_fingerprint(rowptr, colind, feat.shape[0])  # (never hashes: inference calls stay as they were)
         ctx.xcd, xplan = xcdplan.spmm_forward(ctx.fp, rowptr, colind, feat)
+        fwd_sweep = xcdplan.spmm_forward_sweep(ctx.fp, rowptr, colind, feat) if xplan is None else None
         if xplan is not None:
             out = csr_spmm_xcd_raw(xplan, edge_weight_csr, feat)
+        elif fwd_sweep is not None:
+            # a structure of this shape came back before and left its forward layout: both launches go out, guarded by the hash
+            # that is in flight, and the device runs the one that fits (no wait, same bits either way)
+            out = csr_spmm_sweep_forward_raw(fwd_sweep, ctx.fp.dev, rowptr, colind, edge_weight_csr, feat)
         else:
             out = csr_spmm_raw(rowptr, colind, edge_weight_csr, feat)
         need_w = edge_weight_csr is not None and ctx.needs_input_grad[3]
@@ -228,6 +280,13 @@ class SPMMFunction(torch.autograd.Function):
                 grad_feat = csr_spmm_raw(plan.colptr, plan.rowind, w_t, grad_out)
             else:
                 plan = PLANS.get(ctx.fp, rowptr, colind, ctx.n_src)
+                if plan.sightings > 1 and ctx.xcd is None and xcdplan.spmm_forward_sweep_shape(
+                        plan.m, plan.nnz, ctx.n_src, grad_out.shape[1], grad_out.dtype):
+                    # a structure that comes back, of a shape whose FORWARD may walk a sweep layout: build it (once) and make
+                    # the structure the candidate later forward calls of this shape speculate on
+                    from .. import sweepplan
+
+                    sweepplan.register_forward(ctx.fp, rowptr, colind, grad_out.shape[1], grad_out.dtype)
                 split_t, xplan_t = xcdplan.spmm_backward(ctx.fp, plan, grad_out, ctx.xcd is not None)
                 if split_t is not None:
                     # (w stays in CSR order: the plan of the transpose maps its positions through the transpose's perm)

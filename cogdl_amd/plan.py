@@ -250,19 +250,30 @@ def transient():
     return _TRANSIENT > 0
 
 
+# Structures whose FORWARD sweep layout is cached (cogdl_amd/sweepplan.py: FORWARD), by what a call knows of its structure before
+# its hash has landed: (device, m, nnz, n_src) -> Fingerprint key.  One candidate per meta, the latest registered.  A call
+# whose meta has a candidate hashes into device memory as well (Fingerprint.dev), so that the launches behind the hash can
+# compare it with the candidate's key themselves (csrc/common.h: HashGuard).
+CANDIDATES = {}
+_forward_layouts = None  # sweepplan.FORWARD once that module is imported (PlanCache.clear drops it)
+
+
 class Fingerprint:
     """A structure hash in flight: the kernel writes its per-workgroup partials straight into pinned host memory
     (device-visible on ROCm: no memset, no device-to-host copy kernel); an event guards them.  Buffers and events are
     recycled through a small per-device pool when the Fingerprint dies (a pinned allocation per forward call is
-    ~10 us of host time, and a training epoch is launch-bound)."""
-    __slots__ = ("host", "event", "meta", "_key")
+    ~10 us of host time, and a training epoch is launch-bound).
+    dev: the same partials in a [FINGERPRINT_PARTS] int64 DEVICE tensor, ordered by the stream like everything else -- only
+    when a candidate is registered for the call's meta (dev_parts=None), or on request (dev_parts=True: tests); every other
+    call launches the kernel it always launched."""
+    __slots__ = ("host", "event", "meta", "_key", "dev")
 
-    def __init__(self, rowptr, colind, n_cols):
+    def __init__(self, rowptr, colind, n_cols, dev_parts=None):
         dev = rowptr.device
         m, nnz = rowptr.numel() - 1, colind.numel()
         self.meta = (dev.index, m, nnz, int(n_cols))
         self._key = None
-        self.host = self.event = None
+        self.host = self.event = self.dev = None
         if _TAPE is not None and _TAPE.mode == "replay":
             return  # capturing: the plan comes from the tape, nothing is hashed
         _reap_pending()
@@ -274,9 +285,16 @@ class Fingerprint:
             with _lib.on_device(dev):
                 self.event = torch.cuda.Event()
         stream = _lib.current_stream_obj(dev)
+        if dev_parts is None:
+            dev_parts = self.meta in CANDIDATES
         with _lib.on_device(dev):
-            rc = _lib.hip().cogdl_hip_csr_fingerprint(_lib.ptr(rowptr), _lib.ptr(colind), m, nnz,
-                                                      self.host.data_ptr(), stream.cuda_stream)
+            if dev_parts:
+                self.dev = torch.empty(FINGERPRINT_PARTS, dtype=torch.int64, device=dev)
+                rc = _lib.hip().cogdl_hip_csr_fingerprint_dev(_lib.ptr(rowptr), _lib.ptr(colind), m, nnz,
+                                                              self.host.data_ptr(), self.dev.data_ptr(), stream.cuda_stream)
+            else:
+                rc = _lib.hip().cogdl_hip_csr_fingerprint(_lib.ptr(rowptr), _lib.ptr(colind), m, nnz,
+                                                          self.host.data_ptr(), stream.cuda_stream)
             _lib.check(rc, "csr_fingerprint")
             self.event.record(stream)
 
@@ -464,6 +482,9 @@ class PlanCache:
     def clear(self):
         self.lru.clear()
         self.bytes = 0
+        CANDIDATES.clear()  # (the forward sweep layouts live in a cache of their own, outside `bytes`: dropped with the plans)
+        if _forward_layouts is not None:
+            _forward_layouts.clear()
 
 
 PLANS = PlanCache()

@@ -354,6 +354,52 @@ def spmm_backward_sweep(csc, grad_out, round_rows=None):
     return not csc.has_hub_columns()
 
 
+SWEEP_FORWARD_MAX_OUT_OF_ORDER = 1.0 / 8  # a condition, not a tuned number: rows that are an ascending run plus an appended self loop
+                                          # sit at 1 / (degree + 1) (the benchmark's graph: 0.0628); rows in random column order near
+                                          # 1 - H(d) / d (0.78 at 14.8 edges per row) -- their walk has no order to speak of
+
+
+def spmm_forward_sweep_shape(m, nnz, n_src, k, dtype, round_rows=None):
+    """The part of spmm_forward_sweep that needs no layout (the backward pass asks it before it builds one): MODE auto, no
+    transient structure, no plan tape, plan.VERIFY_HITS off (the forward has no host-side hit to verify: it trusts the 64-bit
+    hash on the device), fp32 rows of 512 bytes, a table beyond the eight L2s and of at most 2^23 rows, all rows in one round."""
+    if MODE != "auto" or _plan.transient() or _plan.taping() or _plan.VERIFY_HITS:
+        return False
+    if dtype != torch.float32 or k * 4 != SWEEP_ROW_BYTES or nnz == 0:
+        return False
+    from . import sweepplan
+
+    if n_src > sweepplan.MAX_TABLE_ROWS or n_src * SWEEP_ROW_BYTES < SWEEP_MIN_TABLE_BYTES:
+        return False
+    if round_rows is None:
+        round_rows = sweepplan.round_rows(k, dtype)
+    return m <= round_rows
+
+
+def spmm_forward_sweep(fp, rowptr, colind, x, round_rows=None):
+    """SPMMFunction.forward, asked only when spmm_forward said "ordinary": does the call SPECULATE on the forward sweep layout
+    (cogdl_amd/sweepplan.py: build_forward) of a structure seen before?  -> that layout, or None.  The call's own hash is
+    still in flight, so the host cannot know whether this IS that structure; the device can (the hash kernel runs on the same
+    stream in front of the SpMM): the sweep is enqueued guarded "run if the hash is the layout's", the ordinary launch
+    guarded "run if it is not" (operators/spmm.py: csr_spmm_sweep_forward_raw).  Yes only if: the conditions of
+    spmm_forward_sweep_shape; the stream is not capturing; a candidate with a layout is registered for the call's (device, m,
+    nnz, n_src) and the call hashed into device memory (Fingerprint.dev); the layout has no row above the exact-row bound (the
+    sweep reduces every row sequentially) and at most SWEEP_FORWARD_MAX_OUT_OF_ORDER of its edges behind their row's
+    running maximum.  Never waits, never reads back."""
+    if fp is None or getattr(fp, "dev", None) is None or x.dim() != 2:
+        return None
+    if not spmm_forward_sweep_shape(rowptr.numel() - 1, colind.numel(), x.shape[0], x.shape[1], x.dtype, round_rows):
+        return None
+    from . import sweepplan
+
+    sp = sweepplan.candidate(fp.meta)
+    if sp is None or sp.hash is None or not sweepplan.takeable(sp):
+        return None
+    if torch.cuda.is_current_stream_capturing():
+        return None
+    return sp
+
+
 def gat_forward(fp, rowptr, colind, n_src, row_bytes):
     """FusedGATFunction.forward -> the structure's plan (cut at SPLIT) or None.  row_bytes: None for an operand the kernels refuse.
     H; else S -- a memoised structure and the recorded eager run of cogdl_amd.graphs.capture wait for the key."""

@@ -182,6 +182,24 @@ COGDL_API int cogdl_hip_csr_spmm_sweep(const int32_t *goff, const int32_t *src, 
                                        void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Guarded launches (added within ABI v9: new symbols only).  The sweep needs no sorted rows, only an order inside each group
+ * that keeps every row's own edge order -- so the FORWARD pass may walk a layout of A itself (cogdl_amd/sweepplan.py:
+ * build_forward), cached for a structure seen earlier.  Whether the call at hand passes that structure is decided ON THE DEVICE:
+ * `parts` are the COGDL_HIP_FINGERPRINT_PARTS partials that cogdl_hip_csr_fingerprint_dev has written to device memory on the
+ * same stream (16-byte aligned), `expect` the cached structure's hash.  Every wave sums the partials and compares; with
+ * run_if_equal = 1 the launch does its work on a match and nothing otherwise, with run_if_equal = 0 the other way round.  A
+ * launch that stands down writes nothing -- not `out`, not the workspace.  Enqueue the sweep guarded 1 and the ordinary launch
+ * guarded 0 with the same `out`: exactly one of them computes it, with the bits of cogdl_hip_csr_spmm either way.
+ * Both take f32 with k = 128 only (COGDL_HIP_EUNSUPPORTED otherwise); the other arguments are those of cogdl_hip_csr_spmm_sweep /
+ * cogdl_hip_csr_spmm. */
+COGDL_API int cogdl_hip_csr_spmm_sweep_guarded(const int32_t *goff, const int32_t *src, const void *w, const void *x, void *out,
+                                               int64_t m, int64_t n_src, int64_t n_groups, int r, int64_t k, int64_t nnz,
+                                               int dtype, const uint64_t *parts, uint64_t expect, int run_if_equal, void *stream);
+COGDL_API int cogdl_hip_csr_spmm_guarded(const int32_t *rowptr, const int32_t *colind, const void *val, const void *x,
+                                         void *out, int64_t m, int64_t k, int64_t nnz, int dtype, const uint64_t *parts,
+                                         uint64_t expect, int run_if_equal, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * 64-bit CSR ("big CSR", ABI v7): graphs of 2^31 edges and more -- ogbn-papers100M as CogDL feeds it to GCN
  * (symmetrised + coalesced, cogdl/datasets/ogb.py:50-55: 3.2e9 edges).  The reference cannot represent them: the
  * dispatcher casts row pointers to int32 (utils/spmm_utils.py:106), csr_spmm_cpu walks `int` edge offsets and
@@ -613,6 +631,10 @@ COGDL_API int cogdl_hip_edge_dropout_mask_host(int64_t nnz, int64_t h, float p, 
 #define COGDL_HIP_FINGERPRINT_PARTS 256
 COGDL_API int cogdl_hip_csr_fingerprint(const int32_t *rowptr, const int32_t *colind, int64_t m, int64_t nnz,
                               uint64_t *out_parts, void *stream);
+/* the same, with every partial ALSO stored to dev_parts (device memory, COGDL_HIP_FINGERPRINT_PARTS entries): for the guarded
+ * launches above, which read the hash on the device */
+COGDL_API int cogdl_hip_csr_fingerprint_dev(const int32_t *rowptr, const int32_t *colind, int64_t m, int64_t nnz,
+                                            uint64_t *out_parts, uint64_t *dev_parts, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * coo2csr_index on the GPU: stable sort of the edges by row -> (row_ptr[num_nodes+1], perm[nnz]), perm[j] = COO
