@@ -151,6 +151,8 @@ HIP_SIGNATURES = {
     # random walks (csrc/walk.hip)
     "cogdl_hip_random_walk": ([_vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _u64, _vp, _vp, _vp], _i32),
     "cogdl_hip_node2vec_walk": ([_vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _f64, _i32, _u64, _vp, _vp, _vp, _vp], _i32),
+    "cogdl_hip_metapath_walk": ([_vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i32, _u64, _vp, _vp, _vp, _vp],
+                                _i32),
     # NetSMF path sampling (csrc/netsmf.hip)
     "cogdl_hip_netsmf_sample": ([_vp, _vp, _i64, _i64, _i64, _i64, _i32, _u64, _vp, _vp, _vp, _vp], _i32),
     # top-k personalised PageRank (csrc/ppr.hip)
@@ -190,6 +192,7 @@ HOST_SIGNATURES = {
     "cogdl_host_csr_spmm_f32_i64": ([_vp] * 5 + [_i64, _i64, _i32], _i32),
     "cogdl_host_random_walk": ([_vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _u64, _vp, _vp], _i32),
     "cogdl_host_node2vec_walk": ([_vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _f64, _i32, _u64, _vp, _vp, _vp], _i32),
+    "cogdl_host_metapath_walk": ([_vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i32, _u64, _vp, _vp, _vp], _i32),
     "cogdl_host_netsmf_sample": ([_vp, _vp, _i64, _i64, _i64, _i64, _i32, _u64, _vp, _vp, _vp], _i32),
     "cogdl_host_ppr_plan": ([_i64, _i64, _i64, _f64, _f64, _vp], _i32),
     "cogdl_host_ppr_topk": ([_vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _f64, _i64] + [_vp] * 5, _i32),

@@ -484,4 +484,41 @@ int cogdl_host_node2vec_walk(const int64_t *indptr, const int64_t *indices, int6
     return COGDL_HOST_OK;
 }
 
+int cogdl_host_metapath_walk(const int64_t *seg, const int64_t *indices_t, int64_t num_nodes, int32_t num_types,
+                             int64_t num_edges, const int32_t *node_type, const int64_t *start, const int32_t *walker_path,
+                             int64_t n_walkers, int64_t length, const int32_t *pattern, const int32_t *path_off,
+                             int32_t n_paths, uint64_t seed, int64_t *walks, int32_t *lengths, int *flags) {
+    const int rc = walk_args_status(seg, indices_t, num_nodes, num_edges, start, n_walkers, length, walks, flags);
+    if (rc != COGDL_HOST_OK) return rc;
+    if (num_types < 1 || num_types > 64 || n_paths < 1) return COGDL_HOST_EINVAL;
+    if (n_walkers > 0 && (!walker_path || !pattern || !path_off)) return COGDL_HOST_EINVAL;
+    if (num_nodes > ((int64_t)1 << 56)) return COGDL_HOST_ERANGE;
+    const wk::TypedGraph g = {seg, indices_t, num_nodes, num_edges, num_types};
+    int all = 0;
+#pragma omp parallel for schedule(static) reduction(| : all) if (n_walkers * length >= 4096)
+    for (int64_t w = 0; w < n_walkers; ++w) {
+        int64_t *out = walks + w * length;
+        int err = 0;
+        const int64_t first = start[w];
+        wk::PathCursor pc = wk::metapath_begin(g, node_type, first, walker_path[w], pattern, path_off, n_paths, err);
+        int64_t cur = err ? -1 : first;
+        int32_t n_held = 1;
+        out[0] = first;
+        for (int64_t i = 1; i < length; ++i) {
+            if (err == 0 && cur >= 0) {
+                const int32_t t = wk::metapath_next_type(pc);
+                cur = wk::step_metapath(g, t, seed, w, i, cur, err);
+                n_held += cur >= 0 ? 1 : 0;
+            } else {
+                cur = -1;
+            }
+            out[i] = cur;
+        }
+        if (lengths) lengths[w] = n_held;
+        all |= err;
+    }
+    *flags = all;
+    return COGDL_HOST_OK;
+}
+
 }  // extern "C"

@@ -120,6 +120,62 @@ __global__ __launch_bounds__(kWalkBlock) void node2vec_walk_kernel(wk::Graph g, 
     walk_raise(flags, err > 0 ? err : 0);
 }
 
+// The metapath walk: random_walk_kernel with the typed step.  A step reads seg[cur * T + t] (and its successor) and one entry
+// of indices_t: the same two dependent random loads.  The wanted type does not depend on where the walker stands, so its
+// load (4 bytes of a table of a few dozen entries: an L1/L2 hit) is issued one step ahead and is in flight together with the
+// two loads of the step before it; a copy of the table in LDS would buy a shorter latency for a load that is not on the
+// dependent chain, at the price of a staging pass per wave.  A walker whose walk has ended (or that raised a flag) holds
+// cur = -1, reads nothing and still writes its -1 into the tile: the flush stays one full-width pass.
+__global__ __launch_bounds__(kWalkBlock) void metapath_walk_kernel(wk::TypedGraph g, const int32_t *__restrict__ node_type,
+                                                                   const int64_t *__restrict__ start,
+                                                                   const int32_t *__restrict__ walker_path, int64_t n_walkers,
+                                                                   int64_t length, const int32_t *__restrict__ pattern,
+                                                                   const int32_t *__restrict__ path_off, int32_t n_paths,
+                                                                   uint64_t seed, int64_t *__restrict__ walks,
+                                                                   int32_t *__restrict__ lengths, int *__restrict__ flags) {
+    __shared__ int64_t lds[kWalkBlock / kWave][kWave][kWalkTile + 1];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    int64_t(*stage)[kWalkTile + 1] = lds[wave];
+    const int64_t wave_base = ((int64_t)blockIdx.x * (kWalkBlock / kWave) + wave) * kWave;
+    const int64_t w = wave_base + lane;
+    int64_t first = -1, cur = -1;
+    int err = -1;  // no walker: parked from the start, nothing raised
+    int32_t n_held = 0, t_next = 0;
+    wk::PathCursor pc = {pattern, 1, 0};
+    if (w < n_walkers) {
+        err = 0;
+        first = start[w];
+        pc = wk::metapath_begin(g, node_type, first, walker_path[w], pattern, path_off, n_paths, err);
+        n_held = 1;
+        if (err == 0) {
+            cur = first;
+            t_next = wk::metapath_next_type(pc);  // the type wanted at position 1
+        }
+    }
+    for (int64_t tile0 = 0; tile0 < length; tile0 += kWalkTile) {
+        const int ncols = (int)(length - tile0 < kWalkTile ? length - tile0 : kWalkTile);
+        for (int s = 0; s < ncols; ++s) {
+            const int64_t i = tile0 + s;
+            if (i > 0) {
+                if (err == 0 && cur >= 0) {
+                    const int32_t t = t_next;
+                    t_next = wk::metapath_next_type(pc);
+                    cur = wk::step_metapath(g, t, seed, w, i, cur, err);
+                    n_held += cur >= 0 ? 1 : 0;
+                } else {
+                    cur = -1;
+                }
+            }
+            stage[lane][s] = i == 0 ? first : cur;
+        }
+        wave_lds_sync();
+        walk_flush(stage, lane, wave_base, n_walkers, length, tile0, ncols, walks);
+        wave_lds_sync();
+    }
+    if (lengths && w < n_walkers) lengths[w] = n_held;
+    walk_raise(flags, err > 0 ? err : 0);
+}
+
 static int walk_args_status(const int64_t *indptr, const int64_t *indices, int64_t num_nodes, int64_t num_edges,
                             const int64_t *start, int64_t n_walkers, int64_t length, const int64_t *walks, const int *flags) {
     if (num_nodes < 0 || num_edges < 0 || n_walkers < 0 || length < 1 || !flags) return COGDL_HIP_EINVAL;
@@ -172,5 +228,28 @@ extern "C" int cogdl_hip_node2vec_walk(const int64_t *indptr, const int64_t *ind
     const wk::Graph g = {indptr, indices, num_nodes, num_edges};
     hipLaunchKernelGGL(node2vec_walk_kernel, dim3((unsigned)((n_walkers + kWalkBlock - 1) / kWalkBlock)), dim3(kWalkBlock), 0, s, g,
                        start, n_walkers, length, wk::n2v_weights(p, q), max_trials, seed, walks, fallback_steps, flags);
+    return launch_status();
+}
+
+extern "C" int cogdl_hip_metapath_walk(const int64_t *seg, const int64_t *indices_t, int64_t num_nodes, int32_t num_types,
+                                       int64_t num_edges, const int32_t *node_type, const int64_t *start,
+                                       const int32_t *walker_path, int64_t n_walkers, int64_t length, const int32_t *pattern,
+                                       const int32_t *path_off, int32_t n_paths, uint64_t seed, int64_t *walks,
+                                       int32_t *lengths, int *flags, void *stream) {
+    const int rc = walk_args_status(seg, indices_t, num_nodes, num_edges, start, n_walkers, length, walks, flags);
+    if (rc != COGDL_HIP_OK) return rc;
+    if (num_types < 1 || num_types > 64 || n_paths < 1) return COGDL_HIP_EINVAL;
+    if (n_walkers > 0 && (!walker_path || !pattern || !path_off)) return COGDL_HIP_EINVAL;
+    if (num_nodes > ((int64_t)1 << 56)) return COGDL_HIP_ERANGE;  // (cur * num_types stays a 64-bit offset)
+    hipStream_t s = (hipStream_t)stream;
+    const hipError_t e = fill_u32_async(flags, 0u, 1, s);
+    if (e != hipSuccess) {
+        g_last_hip_error = (int)e;
+        return COGDL_HIP_ELAUNCH;
+    }
+    if (n_walkers == 0) return COGDL_HIP_OK;
+    const wk::TypedGraph g = {seg, indices_t, num_nodes, num_edges, num_types};
+    hipLaunchKernelGGL(metapath_walk_kernel, dim3((unsigned)((n_walkers + kWalkBlock - 1) / kWalkBlock)), dim3(kWalkBlock), 0, s, g,
+                       node_type, start, walker_path, n_walkers, length, pattern, path_off, n_paths, seed, walks, lengths, flags);
     return launch_status();
 }

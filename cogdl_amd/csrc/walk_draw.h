@@ -11,7 +11,7 @@
 //     which neighbour  mulhi64((y << 32) | z, deg): uniform over [0, deg) with a bias below deg / 2^64, and able to
 //                      return deg - 1
 //     accept?          w < A,  A = round(weight / max weight * 2^32) (node2vec rejection sampling; A = 2^32 accepts always)
-// The first-order walk uses trial 0 only.  node2vec uses trials 0 .. max_trials - 1 for its rejection loop and trial
+// The first-order walk and the metapath walk (the first-order draw on a typed row) use trial 0 only.  node2vec uses trials 0 .. max_trials - 1 for its rejection loop and trial
 // `max_trials` for the one draw of the exact fallback: r = mulhi64((y << 32) | z, total weight).
 // Nothing depends on launch shape, thread count or the order in which walkers are processed.
 //
@@ -205,6 +205,86 @@ COGDL_WALK_FN int64_t step_node2vec(const Graph &g, uint64_t seed, int64_t walke
         if (r < acc) return x;
     }
     return v;  // unreachable: r < total = the final acc
+}
+
+// ---------------------------------------------------------------- metapath-constrained walk
+// Typed row layout: seg has n * t + 1 entries, indices[seg[v * t + c] .. seg[v * t + c + 1]) are the neighbours of v whose
+// type is c (cogdl_amd/operators/walk.py: typed_rows), so "a uniform neighbour of the wanted type" is the first-order
+// step on row v * t + c: two dependent loads.  With t == 1 seg is indptr itself.
+enum : int {
+    kBadStartType = 8,  // a start node whose type is not the first item of its metapath
+    kBadPathType = 16   // a wanted type outside [0, t), a metapath id outside [0, n_paths) or a malformed path_off
+};
+
+struct TypedGraph {
+    const int64_t *seg, *indices;
+    int64_t n, e;
+    int32_t t;
+};
+
+// Where a walker is in its metapath: pat[0 .. period) is the schema without its repeated last item, k = position % period.
+struct PathCursor {
+    const int32_t *pat;
+    int32_t period, k;
+};
+
+// Position 0 of walker `start` on metapath `p`: validates the start id, the metapath id, its slice of `pattern` (inside
+// [0, path_off[n_paths]]) and, where node_type is given, the start node's type.  On any failure err is raised and the
+// cursor points at nothing.  Otherwise the cursor stands at position 1.
+COGDL_WALK_FN PathCursor metapath_begin(const TypedGraph &g, const int32_t *node_type, int64_t start, int32_t p,
+                                        const int32_t *pattern, const int32_t *path_off, int32_t n_paths, int &err) {
+    PathCursor c = {pattern, 1, 0};
+    if ((uint64_t)start >= (uint64_t)g.n) {
+        err |= kBadStart;
+        return c;
+    }
+    if ((uint32_t)p >= (uint32_t)n_paths) {
+        err |= kBadPathType;
+        return c;
+    }
+    const int32_t lo = path_off[p], hi = path_off[p + 1], total = path_off[n_paths];
+    if (lo < 0 || hi <= lo || hi > total) {
+        err |= kBadPathType;
+        return c;
+    }
+    c.pat = pattern + lo;
+    c.period = hi - lo;
+    c.k = c.period == 1 ? 0 : 1;
+    if (node_type && node_type[start] != c.pat[0]) err |= kBadStartType;
+    return c;
+}
+
+// The type wanted at the cursor's position, pattern[path_off[p] + i % period]; the cursor moves on to position i + 1.
+// Independent of where the walker stands: a kernel can issue it one step ahead.
+COGDL_WALK_FN int32_t metapath_next_type(PathCursor &c) {
+    const int32_t t = c.pat[c.k];
+    c.k = c.k + 1 == c.period ? 0 : c.k + 1;
+    return t;
+}
+
+// One step of the metapath walk: from `cur` to a uniformly drawn neighbour of type `t` (the draw of the first-order walk).
+// -1: the walk has ended (no neighbour of that type: the reference's `break`), had ended before (cur < 0), or a flag is up --
+// such a walker reads nothing.
+COGDL_WALK_FN int64_t step_metapath(const TypedGraph &g, int32_t t, uint64_t seed, int64_t walker, int64_t step, int64_t cur,
+                                    int &err) {
+    if (err || cur < 0) return -1;
+    if ((uint32_t)t >= (uint32_t)g.t) {
+        err |= kBadPathType;
+        return -1;
+    }
+    const int64_t r = cur * g.t + t;
+    const int64_t beg = g.seg[r], end = g.seg[r + 1], len = end - beg;
+    if (beg < 0 || end > g.e || len < 0) {
+        err |= kBadRowPtr;
+        return -1;
+    }
+    if (len == 0) return -1;
+    const int64_t x = g.indices[beg + draw_below(draw(seed, walker, step, 0u), (uint64_t)len)];
+    if ((uint64_t)x >= (uint64_t)g.n) {
+        err |= kBadNeighbour;
+        return -1;
+    }
+    return x;
 }
 
 }  // namespace cogdl_walk

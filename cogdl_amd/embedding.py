@@ -5,12 +5,14 @@ library's skip-gram operator -- what the reference's DeepWalk / Node2vec do thro
     deepwalk(graph_or_csr, dim, walk_length, walk_num, window, epochs)      -> float32 [N, dim]
     node2vec(graph_or_csr, dim, walk_length, walk_num, window, epochs, p, q) -> float32 [N, dim]
     netsmf(graph_or_csr, dim, window, negative, rounds)                     -> float32 [N, dim]
+    metapath2vec(graph_or_csr, node_type, schema, dim, walk_length, walk_num, window, epochs) -> float32 [N, dim]
 
 `graph_or_csr` is a cogdl Graph (its row_indptr / col_indices are used on the device they live on) or an
 (indptr, indices) pair of int64 tensors.  Each of the walk_num passes starts one walk at every node, in an order shuffled
 per pass (as the reference does); the passes' rows follow each other, which is the order the trainer consumes them in.
 Differences from the reference: the draws come from Philox, not from numpy's / gensim's generators; at a node without
-out-neighbours the walker stays (the reference ends the walk); node2vec ignores edge weights.
+out-neighbours the walker stays (the reference ends the walk); node2vec ignores edge weights.  metapath2vec (the walk of
+cogdl/models/emb/metapath2vec.py:87-125) ends a walk where no neighbour has the wanted type, as the reference does.
 
 netsmf is the matrix-factorisation member of the family (cogdl/models/emb/netsmf.py): path samples counted into a sparse
 matrix, the sparsifier's log transform, a randomized SVD -- all three from cogdl_amd/operators/netsmf.py, nothing trained.
@@ -20,7 +22,7 @@ import math
 import torch
 
 from .operators.sgns import skipgram
-from .operators.walk import _seed, node2vec_walk, random_walk
+from .operators.walk import _seed, metapath_walk, node2vec_walk, parse_schema, random_walk
 
 
 def _csr(graph_or_csr):
@@ -63,6 +65,49 @@ def node2vec(graph_or_csr, dim=128, walk_length=80, walk_num=40, window=5, epoch
     """node2vec: second-order walks with return parameter p and in-out parameter q, then skip-gram."""
     return _embed(lambda ip, ix, st, sd: node2vec_walk(ip, ix, st, walk_length, p=p, q=q, seed=sd), graph_or_csr, dim, walk_length,
                   walk_num, window, epochs, seed, negative, alpha, min_alpha, sample, workers)
+
+
+def metapath2vec(graph_or_csr, node_type, schema, dim=128, walk_length=80, walk_num=20, window=5, epochs=10, seed=None,
+                 negative=5, alpha=0.025, min_alpha=1e-4, sample=1e-3, workers=0, nodes=None, return_walks=False):
+    """metapath2vec: walks that follow a node-type schema ("0-1-0,0-2-0,1-0-2-0-1", or a list of integer lists), then
+    skip-gram.  -> float32 [N, dim] on the graph's device.  For every metapath, each of the walk_num passes starts one walker
+    at every node of the metapath's first type, in an order shuffled per pass; a walk that meets a node without a neighbour of
+    the wanted type ends there (the rest of its row is -1, which skipgram skips).  schema="No" is the reference's
+    type-agnostic walk: one metapath over a single type.  `nodes` (int64 ids) restricts the start nodes (the reference starts
+    at the nodes that occur in an edge); return_walks=True also returns the int64 [W, walk_length] walks.  A node that no
+    walk visits keeps its initial row."""
+    walk_num = int(walk_num)
+    if walk_num < 1:
+        raise ValueError("walk_num must be >= 1 (got %d)" % walk_num)
+    indptr, indices = _csr(graph_or_csr)
+    dev, n = indptr.device, indptr.numel() - 1
+    if isinstance(schema, str) and schema == "No":
+        node_type, paths = torch.zeros(n, dtype=torch.int32, device=dev), [[0, 0]]
+    else:
+        node_type, paths = torch.as_tensor(node_type).to(dev).contiguous(), parse_schema(schema)
+        if node_type.dtype not in (torch.int32, torch.long):
+            raise ValueError("node_type must be an integer tensor (got %s)" % node_type.dtype)
+    if node_type.dim() != 1 or node_type.numel() != n:
+        raise ValueError("node_type must have one entry per node (%d)" % n)
+    seed = _seed(seed)
+    mask = torch.ones(n, dtype=torch.bool, device=dev)
+    if nodes is not None:
+        mask = torch.zeros(n, dtype=torch.bool, device=dev)
+        mask[torch.as_tensor(nodes, dtype=torch.long, device=dev)] = True
+    firsts = [torch.nonzero(mask & (node_type == items[0])).flatten().cpu() for items in paths]
+    gen = torch.Generator().manual_seed(seed % (2 ** 63))
+    start, which = [], []
+    for _ in range(walk_num):
+        for p, first in enumerate(firsts):
+            start.append(first[torch.randperm(first.numel(), generator=gen)])
+            which.append(torch.full((first.numel(),), p, dtype=torch.int32))
+    start, which = torch.cat(start).to(dev), torch.cat(which).to(dev)
+    if start.numel() == 0:
+        raise ValueError("metapath2vec: no node has the first type of a metapath of %r" % (schema,))
+    walks = metapath_walk(indptr, indices, node_type, start, paths, walk_length, walker_path=which, seed=(seed + 1) & (2 ** 64 - 1))
+    syn0, _ = skipgram(walks, n, dim=dim, window=window, negative=negative, epochs=epochs, alpha=alpha, min_alpha=min_alpha,
+                       sample=sample, seed=(seed + 2) & (2 ** 64 - 1), workers=workers)
+    return (syn0, walks) if return_walks else syn0
 
 
 def netsmf(graph_or_csr, dim=128, window=10, negative=1, rounds=100, seed=None):

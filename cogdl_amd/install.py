@@ -40,7 +40,7 @@ _finder = None
 
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
             metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False, readout=False,
-            relational=False, genconv=False, disengcn=False, contrast=False, netsmf=False):
+            relational=False, genconv=False, disengcn=False, contrast=False, netsmf=False, metapath=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -125,6 +125,15 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     sparsifier and the randomized SVD run there too (cogdl_amd/operators/netsmf.py), with the same return value
     (features_matrix as numpy [N, dim], or the dict with return_dict=True).  A graph whose edge weights are not all equal and
     a graph without edges reach the reference's forward.
+    metapath=True rebinds Metapath2vec.forward in cogdl.models.emb.metapath2vec (opt-in: the draws are Philox's, not `random`'s
+    and gensim's; the start order differs; `worker` is ignored) to cogdl_amd.metapath_compat: the DiGraph's CSR is built on the
+    device of edge_index, the walk_num x nodes x metapaths walks come from the library's metapath walk (typed row layout, HIP
+    kernel for a graph on the GPU, the OpenMP host twin otherwise) instead of an interpreted loop over networkx neighbour
+    lists, and the skip-gram operator trains on them; the return value is the reference's (float32 numpy, one row per node
+    that occurs in an edge, in networkx insertion order; KeyError for a node that no walk visits).  The reference module
+    imports gensim, so where gensim is absent cogdl_amd.gensim_compat is registered first, as skipgram=True does.  A schema
+    item that is not an integer, a metapath whose first item differs from its last and a data.pos that is not an integer
+    tensor reach the reference's forward.
     linear=True additionally routes torch.nn.functional.linear -- i.e. the unchanged nn.Linear inside every CogDL
     layer -- through cogdl_amd.linear (hand-written MFMA weight gradient for full-graph shapes)."""
     global _finder
@@ -216,6 +225,13 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
         _import_target(netsmf_compat._MODULE, "netsmf")
         if not netsmf_compat.install():
             raise _lib_error("install(netsmf=True): NetSMF.forward could not be rebound")
+    if metapath:
+        from . import metapath_compat
+
+        _serve_gensim_where_absent()  # (cogdl.models.emb.metapath2vec imports gensim)
+        _import_target(metapath_compat._MODULE, "metapath")
+        if not metapath_compat.install():
+            raise _lib_error("install(metapath=True): Metapath2vec.forward could not be rebound")
     su = sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):
@@ -373,10 +389,8 @@ def _node2vec_forward(self, graph, return_dict=False):
     return _embedding_matrix(self, graph, return_dict, emb)
 
 
-def _install_skipgram():
-    """gensim is served by cogdl_amd.gensim_compat where the real package is absent (the real one wins where it exists), then
-    the two models are imported and their forward rebound.  Without the cogdl package only the module registration
-    happens."""
+def _serve_gensim_where_absent():
+    """gensim is served by cogdl_amd.gensim_compat where the real package is absent (the real one wins where it exists)."""
     from . import gensim_compat
 
     if getattr(sys.modules.get("gensim"), "__name__", None) is None:  # not imported yet (or marked absent)
@@ -385,6 +399,12 @@ def _install_skipgram():
             importlib.import_module("gensim")
         except Exception:
             gensim_compat.register()
+
+
+def _install_skipgram():
+    """The gensim registration step, then the two models are imported and their forward rebound.  Without the cogdl package
+    only the module registration happens."""
+    _serve_gensim_where_absent()
     try:
         importlib.import_module("cogdl")
     except ImportError:

@@ -8,6 +8,7 @@
     sample.py        sample_adj_c, subgraph_c, coo2csr_cpu, coo2csr_cpu_index  (cogdl/operators/sample.py)
 
     walk.py          random_walk, node2vec_walk (also exported here)   (cogdl/utils/sampling.py, models/emb/node2vec.py)
+                     typed_rows, metapath_walk (also exported here)    (models/emb/metapath2vec.py:87-125)
     ppr.py           topk_ppr, full_ppr (also exported here)           (cogdl/utils/ppr_utils.py)
     sgns.py          skipgram (also exported here)                     (gensim's Word2Vec(sg=1) in models/emb/deepwalk.py)
     readout.py       segment_ptr, segment_pool, sort_pool (also exported here)   (cogdl/utils/utils.py batch_*_pooling,
@@ -32,7 +33,7 @@ is missing; `sample` only needs libcogdl_host.so and is safe in forked CPU worke
 
 
 def __getattr__(name):
-    if name in ("random_walk", "node2vec_walk"):
+    if name in ("random_walk", "node2vec_walk", "typed_rows", "metapath_walk"):
         from . import walk
 
         return getattr(walk, name)

@@ -14,6 +14,13 @@ Rules the reference leaves open or that are easy to get wrong (include/cogdl_hip
   * a start or neighbour id outside [0, N) raises BackendError; nothing is read out of bounds;
   * `seed=None` draws the seed from torch's default generator: `torch.manual_seed` makes a run reproducible, successive
     calls differ.
+
+`metapath_walk` follows a node-type schema (the step of cogdl/models/emb/metapath2vec.py:87-106; gatne.py and hin2vec.py use
+the same one) on the typed row layout of `typed_rows`: every row reordered by the type of the neighbour, so "a uniform neighbour
+of the wanted type" is two dependent loads whatever the degree.  Same twins (cogdl_hip_metapath_walk /
+cogdl_host_metapath_walk, step_metapath of csrc/walk_draw.h), same draws: with one type and no dead ends it returns
+random_walk's array.  Unlike the walks above it ENDS where no neighbour has the wanted type, as the reference does: the rest of
+the row holds -1.
 """
 import collections
 import weakref
@@ -27,7 +34,9 @@ from .. import _lib
 NODE2VEC_TRIALS = 0
 
 _FLAG_TEXT = ((1, "a start id lies outside [0, %d)"), (2, "a neighbour id lies outside [0, %d)"),
-              (4, "indptr does not describe rows inside indices (%d nodes)"))
+              (4, "indptr does not describe rows inside indices (%d nodes)"),
+              (8, "a start node's type is not the first type of its metapath (%d nodes)"),
+              (16, "a wanted type or a metapath id lies outside its range (%d nodes)"))
 
 
 def _graph_args(name, indptr, indices, start, length):
@@ -170,3 +179,164 @@ def node2vec_walk(indptr, indices, start, length, p=1.0, q=1.0, seed=None, retur
         _lib.check_host(rc, "node2vec_walk")
     raise_for_flags("node2vec_walk", flags.item(), n)
     return (walks, fallback) if return_fallback else walks
+
+
+# ---------------------------------------------------------------------------------------------------- metapath walk
+MAX_TYPES = 64
+_TYPED = collections.OrderedDict()  # (id(indptr), id(indices), id(node_type), T) -> weak refs, state, (seg, indices_t, int32 types)
+_TYPED_MAX = 8
+
+
+def _typed_state(indptr, indices, node_type):
+    return _state(indptr, indices) + (node_type._version, node_type.data_ptr(), node_type.numel())
+
+
+def _typed_layout(indptr, indices, node_type, num_types=None):
+    name = "typed_rows"
+    if not (torch.is_tensor(indptr) and torch.is_tensor(indices) and torch.is_tensor(node_type)):
+        raise _lib.BackendError("%s: indptr / indices / node_type must be tensors" % name)
+    if indptr.dtype != torch.long or indices.dtype != torch.long:
+        raise _lib.BackendError("%s: indptr / indices must be int64 (got %s / %s)" % (name, indptr.dtype, indices.dtype))
+    if node_type.dtype not in (torch.int32, torch.long):
+        raise _lib.BackendError("%s: node_type must be int32 or int64 (got %s)" % (name, node_type.dtype))
+    if indptr.dim() != 1 or indices.dim() != 1 or node_type.dim() != 1 or indptr.numel() < 1:
+        raise _lib.BackendError("%s: indptr / indices / node_type must be 1-D (indptr non-empty)" % name)
+    if indices.device != indptr.device or node_type.device != indptr.device:
+        raise _lib.BackendError("%s: tensors on different devices: %s, %s, %s" % (name, indptr.device, indices.device, node_type.device))
+    if not (indptr.is_contiguous() and indices.is_contiguous() and node_type.is_contiguous()):
+        raise _lib.BackendError("%s: indptr / indices / node_type must be contiguous" % name)
+    n, e = indptr.numel() - 1, indices.numel()
+    if node_type.numel() != n:
+        raise _lib.BackendError("%s: node_type must have one entry per node (%d, got %d)" % (name, n, node_type.numel()))
+    if num_types is None:
+        num_types = int(node_type.max()) + 1 if n else 1
+    t = int(num_types)
+    if t < 1 or t > MAX_TYPES:
+        raise _lib.BackendError("%s: the number of node types must be in [1, %d] (got %d)" % (name, MAX_TYPES, t))
+    if n * t > 2 ** 31 - 2:
+        raise _lib.BackendError("%s: nodes x types = %d exceeds 2^31 - 2" % (name, n * t))
+    key = (id(indptr), id(indices), id(node_type), t)
+    hit = _TYPED.get(key)
+    if hit is not None:
+        if (hit[0]() is indptr and hit[1]() is indices and hit[2]() is node_type
+                and hit[3] == _typed_state(indptr, indices, node_type)):
+            _TYPED.move_to_end(key)
+            seg, indices_t, types32 = hit[4]  # (None: the caller's own tensor, which the cache must not keep alive)
+            return (indptr if seg is None else seg, indices if indices_t is None else indices_t,
+                    node_type if types32 is None else types32)
+        del _TYPED[key]
+    if n and (int(node_type.min()) < 0 or int(node_type.max()) >= t):
+        raise _lib.BackendError("%s: a node type lies outside [0, %d)" % (name, t))
+    if int(indptr[0]) != 0 or int(indptr[-1]) != e or (n and bool((indptr[1:] < indptr[:-1]).any())):
+        raise _lib.BackendError("%s: indptr is not a row pointer over indices" % name)
+    if e and (int(indices.min()) < 0 or int(indices.max()) >= n):
+        raise _lib.BackendError("%s: a neighbour id lies outside [0, %d)" % (name, n))
+    types32 = node_type if node_type.dtype == torch.int32 else node_type.to(torch.int32)
+    if t == 1:
+        value = (indptr, indices, types32)
+    else:
+        from ..graph_build import coo2csr_index
+
+        row = torch.repeat_interleave(torch.arange(n, device=indptr.device), indptr[1:] - indptr[:-1])
+        seg, perm = coo2csr_index(row * t + node_type[indices].long(), None, n * t)  # stable: the order inside a type is kept
+        value = (seg, indices[perm].contiguous(), types32)
+    try:
+        _TYPED[key] = (weakref.ref(indptr), weakref.ref(indices), weakref.ref(node_type),
+                       _typed_state(indptr, indices, node_type),
+                       (None if t == 1 else value[0], None if t == 1 else value[1], None if types32 is node_type else types32))
+    except TypeError:
+        pass
+    while len(_TYPED) > _TYPED_MAX:
+        _TYPED.popitem(last=False)
+    return value
+
+
+def typed_rows(indptr, indices, node_type, num_types=None):
+    """-> (seg int64 [N * T + 1], indices_t): `indices` with every row reordered by the type of the neighbour (stable inside a
+    type), indices_t[seg[v * T + t] : seg[v * T + t + 1]] the neighbours of v that have type t; seg[v * T] == indptr[v].
+    T = num_types (default: max(node_type) + 1), at most 64.  With T == 1 the result is (indptr, indices) itself.  Built once
+    per structure with coo2csr_index on the key row * T + node_type[col] and cached on the three tensor objects (weak
+    references, vouched for by version counters and data pointers)."""
+    return _typed_layout(indptr, indices, node_type, num_types)[:2]
+
+
+def parse_schema(schema):
+    """The reference's schema string ("0-1-0,0-2-0,1-0-2-0-1") or a list of integer lists -> list of integer lists.  Every
+    metapath needs at least two items and must end on the type it starts with."""
+    if isinstance(schema, str):
+        try:
+            paths = [[int(item) for item in path.split("-")] for path in schema.split(",")]
+        except ValueError:
+            raise ValueError("metapath_walk: schema items must be integers (got %r)" % schema) from None
+    else:
+        paths = []
+        for path in schema:
+            items = list(path)
+            if any(isinstance(item, bool) or int(item) != item for item in items):
+                raise ValueError("metapath_walk: schema items must be integers (got %r)" % (path,))
+            paths.append([int(item) for item in items])
+    if not paths:
+        raise ValueError("metapath_walk: the schema holds no metapath")
+    for path in paths:
+        if len(path) < 2:
+            raise ValueError("metapath_walk: a metapath needs at least two items (got %r)" % (path,))
+        if path[0] != path[-1]:
+            raise ValueError("metapath_walk: a metapath must end on the type it starts with (got %r)" % (path,))
+    return paths
+
+
+def metapath_walk(indptr, indices, node_type, start, schema, length, walker_path=None, seed=None, return_lengths=False):
+    """Walks that follow a node-type schema (the rule of cogdl/models/emb/metapath2vec.py:87-106) -> int64 [len(start), length]
+    on the graph's device.  Walker w follows metapath walker_path[w] of `schema` (one metapath: walker_path may be None); at
+    position i it moves to a uniformly drawn neighbour of type items[i % (len(items) - 1)].  Where there is none the walk
+    ends and the rest of the row holds -1 (padding for `skipgram`).  A start node must have the first type of its metapath.
+    return_lengths=True also returns the int32 [len(start)] number of positions that hold a node."""
+    name = "metapath_walk"
+    paths = parse_schema(schema)
+    indptr, indices, start, length = _graph_args(name, indptr, indices, start, length)
+    if torch.is_tensor(node_type):
+        node_type = node_type if node_type.is_contiguous() else node_type.contiguous()
+    else:
+        node_type = torch.as_tensor(node_type, device=indptr.device)
+    seg, indices_t, types32 = _typed_layout(indptr, indices, node_type)
+    dev, n, e, w = indptr.device, indptr.numel() - 1, indices.numel(), start.numel()
+    t = (seg.numel() - 1) // n if n else 1
+    for path in paths:
+        if min(path) < 0 or max(path) >= t:
+            raise ValueError("%s: a schema item lies outside [0, %d) (metapath %r)" % (name, t, path))
+    if walker_path is None:
+        if len(paths) != 1:
+            raise ValueError("%s: walker_path is needed with %d metapaths" % (name, len(paths)))
+        walker_path = torch.zeros(w, dtype=torch.int32, device=dev)
+    else:
+        if not torch.is_tensor(walker_path):
+            walker_path = torch.as_tensor(walker_path, device=dev)
+        if walker_path.dtype not in (torch.int32, torch.long) or walker_path.dim() != 1 or walker_path.numel() != w:
+            raise _lib.BackendError("%s: walker_path must be an int32 or int64 [%d] tensor" % (name, w))
+        if walker_path.device != dev:
+            raise _lib.BackendError("%s: tensors on different devices: %s vs %s" % (name, dev, walker_path.device))
+        if walker_path.dtype != torch.int32:
+            if w and (int(walker_path.min()) < -2 ** 31 or int(walker_path.max()) >= 2 ** 31):
+                raise _lib.BackendError("%s: a metapath id lies outside [0, %d)" % (name, len(paths)))
+            walker_path = walker_path.to(torch.int32)
+        walker_path = walker_path.contiguous()
+    pattern = torch.tensor([item for path in paths for item in path[:-1]], dtype=torch.int32).to(dev)
+    off = [0]
+    for path in paths:
+        off.append(off[-1] + len(path) - 1)
+    path_off = torch.tensor(off, dtype=torch.int32).to(dev)
+    seed = _seed(seed)
+    walks = torch.empty((w, length), dtype=torch.long, device=dev)
+    lengths = torch.empty(w, dtype=torch.int32, device=dev) if return_lengths else None
+    flags = torch.empty(1, dtype=torch.int32, device=dev)
+    args = (_lib.ptr(seg), _lib.ptr(indices_t), n, t, e, _lib.ptr(types32), _lib.ptr(start), _lib.ptr(walker_path), w, length,
+            _lib.ptr(pattern), _lib.ptr(path_off), len(paths), seed, _lib.ptr(walks), _lib.ptr(lengths), _lib.ptr(flags))
+    if dev.type == "cuda":
+        with _lib.on_device(dev):
+            rc = _lib.hip().cogdl_hip_metapath_walk(*args, _lib.stream_of(indptr))
+        _lib.check(rc, name)
+    else:
+        rc = _lib.host().cogdl_host_metapath_walk(*args)
+        _lib.check_host(rc, name)
+    raise_for_flags(name, flags.item(), n)
+    return (walks, lengths) if return_lengths else walks

@@ -935,6 +935,40 @@ COGDL_API int cogdl_hip_node2vec_walk(const int64_t *indptr, const int64_t *indi
                             uint64_t seed, int64_t *walks, int32_t *fallback_steps, int *flags, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Metapath-constrained random walk (csrc/walk.hip: metapath_walk_kernel), replacing the interpreted loop of
+ * cogdl/models/emb/metapath2vec.py:87-125 (_walk / _simulate_walks; gatne.py:277-336 and hin2vec.py:60-82 use the same step).
+ * Stream-ordered, one launch (plus one word fill), no atomics, no workspace.  Host twin with identical results:
+ * cogdl_host_metapath_walk (include/cogdl_host.h).
+ *   Typed layout   T = num_types node types.  seg: int64[num_nodes * T + 1]; indices_t[seg[v * T + t] .. seg[v * T + t + 1])
+ *                  are the neighbours of v whose type is t, so seg[v * T] is the row pointer of v and seg[num_nodes * T] =
+ *                  num_edges (cogdl_amd/operators/walk.py: typed_rows builds it with cogdl_hip_coo2csr_index).  With T = 1
+ *                  (seg, indices_t) is the plain CSR.
+ *   Metapaths      pattern / path_off: int32; metapath p is pattern[path_off[p] .. path_off[p + 1]), the node types of one
+ *                  PERIOD: the schema "1-0-2-0-1" is (1, 0, 2, 0), its repeated last item left out.  path_off[n_paths + 1]
+ *                  entries, increasing from >= 0.  walker_path[w] in [0, n_paths) is the metapath of walker w.
+ *   Walk           walks[w, 0] = start[w].  At position i >= 1 the wanted type is t = pattern[path_off[p] + i mod P], P the
+ *                  period (the reference's schema_items[len(walk) % (len(schema_items) - 1)]), and the walker moves to a
+ *                  uniformly drawn entry of the segment (v, t), multiplicity counting.  An empty segment ENDS the walk: this
+ *                  position and every later one hold -1 (the reference's `break`), and the walker reads nothing more.
+ *                  lengths: NULL, or int32[W] receiving the number of positions that hold a node (1 for a walker that raised
+ *                  a flag at position 0).
+ *   Randomness     the draw of cogdl_hip_random_walk: Philox4x32-10 of (seed, w, i, trial 0).  With T = 1, the one metapath
+ *                  (0) and a graph without dead ends the result equals cogdl_hip_random_walk(restart_p = 0) bit for bit.
+ *   node_type      NULL, or int32[num_nodes]: then the type of start[w] must be pattern[path_off[p]] (flag bit 3): one load
+ *                  per walker.
+ *   flags          DEVICE int, zeroed by the call: bits 0 .. 2 as in cogdl_hip_random_walk (bit 2 for a segment that is not
+ *                  a range inside [0, num_edges]), bit 3 (8) a start node of the wrong type, bit 4 (16) a wanted type outside
+ *                  [0, T), a walker_path entry outside [0, n_paths) or a malformed path_off.  A walker that raises one writes
+ *                  -1 from then on and reads nothing; nothing is read out of bounds.  Non-zero marks an invalid result; when
+ *                  several conditions occur in one call a bit may be missing, the word is never zero then.
+ *   num_types outside [1, 64], n_paths < 1, a null walker_path / pattern / path_off with W > 0: COGDL_HIP_EINVAL.
+ * ------------------------------------------------------------------------------------- */
+COGDL_API int cogdl_hip_metapath_walk(const int64_t *seg, const int64_t *indices_t, int64_t num_nodes, int32_t num_types,
+                            int64_t num_edges, const int32_t *node_type, const int64_t *start, const int32_t *walker_path,
+                            int64_t n_walkers, int64_t length, const int32_t *pattern, const int32_t *path_off,
+                            int32_t n_paths, uint64_t seed, int64_t *walks, int32_t *lengths, int *flags, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * NetSMF path sampling on a GPU-resident CSR graph (csrc/netsmf.hip): int64 indptr[num_nodes + 1] / indices[num_edges], unit
  * weights; result int32 out_row / out_col of window * n_samples entries each.
  * Stream-ordered, one launch (plus one word fill), no host round trip, no atomics, no workspace; hipGraph-capturable.

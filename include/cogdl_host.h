@@ -102,6 +102,21 @@ COGDL_HOST_API int cogdl_host_node2vec_walk(const int64_t *indptr, const int64_t
                                             double p, double q, int max_trials, uint64_t seed, int64_t *walks,
                                             int32_t *fallback_steps, int *flags);
 
+/* Metapath-constrained random walk on the typed row layout, the host twin of cogdl_hip_metapath_walk (include/cogdl_hip.h,
+ * where the contract is spelled out): same arguments minus the stream, and for equal inputs and seed EXACTLY the arrays the
+ * GPU returns -- both run step_metapath of csrc/walk_draw.h.  seg: int64[num_nodes * num_types + 1], indices_t the
+ * neighbours ordered by type inside each row; pattern / path_off / walker_path: int32, one period per metapath; an empty
+ * segment ends the walk and the rest of the row holds -1; lengths: NULL, or int32[W].  OpenMP over the walkers; the result
+ * does not depend on the number of threads.  *flags (host int): bits 0 .. 2 as above, bit 3 (8) a start node whose type is
+ * not the first of its metapath (node_type non-NULL), bit 4 (16) a wanted type outside [0, num_types), a walker_path entry
+ * outside [0, n_paths) or a malformed path_off.  num_types outside [1, 64], n_paths < 1, a null walker_path / pattern /
+ * path_off with W > 0: COGDL_HOST_EINVAL. */
+COGDL_HOST_API int cogdl_host_metapath_walk(const int64_t *seg, const int64_t *indices_t, int64_t num_nodes,
+                                            int32_t num_types, int64_t num_edges, const int32_t *node_type,
+                                            const int64_t *start, const int32_t *walker_path, int64_t n_walkers,
+                                            int64_t length, const int32_t *pattern, const int32_t *path_off,
+                                            int32_t n_paths, uint64_t seed, int64_t *walks, int32_t *lengths, int *flags);
+
 /* NetSMF path sampling, the host twin of cogdl_hip_netsmf_sample (include/cogdl_hip.h, where the contract is spelled out):
  * same arguments minus the stream, and for equal inputs and seed EXACTLY the arrays the GPU returns -- both run
  * csrc/netsmf_law.h.  out_row / out_col: int32[window * n_samples], sample (s, r) at (r - 1) * n_samples + (s - first_sample).

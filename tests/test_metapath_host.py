@@ -1,0 +1,415 @@
+"""The metapath walk without a GPU: typed_rows, metapath_walk on the host twin (libcogdl_host.so) and the golden record of
+the reference's own walk.  The GPU kernel returns the same arrays bit for bit (tests/test_metapath_gpu.py), so the
+distribution tests here cover both.
+
+Distribution tests follow tests/test_walk_host.py: Pearson's chi-square against the exact law (multiplicity counts), failing
+above the 1 - 1e-6 quantile with (cells - 1) degrees of freedom; seeds are fixed, so the outcome is deterministic.
+
+Batching: walker w draws from (seed, w, step), so a PREFIX of the walkers, or other walkers starting elsewhere, change
+nothing (the entry point has no walker offset: a later batch is numbered from 0 again, as for random_walk)."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+from scipy.stats import chi2
+
+import _metapath_cases as cases
+from cogdl_amd import _lib
+from cogdl_amd.operators import metapath_walk, random_walk, typed_rows
+from cogdl_amd.operators import walk as walk_mod
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "metapath_corridor.npz")
+QUANTILE = 1.0 - 1e-6
+LENGTHS = [1, 2, 7, 8, 9, 16, 17]
+WALKERS = [0, 1, 63, 64, 65, 256, 257]
+
+
+def schemas_for(node_type):
+    """Periods 1, 2 and 4, and calls with two and three metapaths."""
+    out = ["0-0", "0-1-0", "0-1-0-1-0", "0-1-0,1-0-1"]
+    if int(node_type.max()) >= 2:
+        out += ["1-0-2-0-1", "0-1-0,0-2-0,1-0-2-0-1"]
+    else:
+        out += ["0-1-0,1-1,1-0-1-0-1"]
+    return out
+
+
+@pytest.mark.parametrize("name", sorted(cases.CASES))
+def test_checker_passes_on_every_graph_and_schema(name):
+    indptr, indices, node_type, n = cases.CASES[name]()
+    for k, schema in enumerate(schemas_for(node_type)):
+        paths = walk_mod.parse_schema(schema)
+        start, which = cases.starts_for(node_type, paths, repeat=3)
+        mixed = torch.randperm(start.numel(), generator=torch.Generator().manual_seed(k))  # a mixed walker_path
+        start, which = start[mixed], which[mixed]
+        walks, lengths = metapath_walk(indptr, indices, node_type, start, schema, 21, walker_path=which, seed=11 + k,
+                                       return_lengths=True)
+        assert walks.dtype == torch.int64 and tuple(walks.shape) == (start.numel(), 21) and walks.device.type == "cpu"
+        assert lengths.dtype == torch.int32 and tuple(lengths.shape) == (start.numel(),)
+        cases.check_walks(indptr, indices, node_type, start, paths, which, walks, lengths)
+        as_lists = metapath_walk(indptr, indices, node_type, start, paths, 21, walker_path=which.long(), seed=11 + k)
+        assert torch.equal(as_lists, walks), "a list schema / int64 walker_path gives another array"
+
+
+def test_known_walks_on_the_typed_path():
+    indptr, indices, node_type, n = cases.typed_path()
+    # from the sink 7 (type 1) "1-0-1" wants type 0 next: 7 has no out-edge, the walk ends at once
+    walks, lengths = metapath_walk(indptr, indices, node_type, torch.tensor([7, 8]), [[1, 0, 1], [0, 1, 0]], 5,
+                                   walker_path=torch.tensor([0, 1], dtype=torch.int32), seed=0, return_lengths=True)
+    assert walks.tolist() == [[7, -1, -1, -1, -1], [8, -1, -1, -1, -1]] and lengths.tolist() == [1, 1]
+    # "0-0" from a type-0 node: every neighbour has type 1
+    assert metapath_walk(indptr, indices, node_type, torch.tensor([2]), "0-0", 3, seed=0).tolist() == [[2, -1, -1]]
+
+
+@pytest.mark.parametrize("length", LENGTHS)
+@pytest.mark.parametrize("walkers", WALKERS)
+def test_size_sweep(length, walkers):
+    indptr, indices, node_type, n = cases.random_typed()
+    schema = "0-1-0,0-2-0,1-0-2-0-1"
+    paths = walk_mod.parse_schema(schema)
+    start, which = cases.starts_for(node_type, paths, repeat=2)
+    assert start.numel() >= 257
+    start, which = start[:walkers], which[:walkers]
+    walks, lengths = metapath_walk(indptr, indices, node_type, start, schema, length, walker_path=which, seed=5,
+                                   return_lengths=True)
+    assert tuple(walks.shape) == (walkers, length) and walks.dtype == torch.int64
+    cases.check_walks(indptr, indices, node_type, start, paths, which, walks, lengths)
+
+
+def no_dead_end_graph():
+    rng = np.random.default_rng(8)
+    n = 500
+    row = np.concatenate([np.arange(n), rng.integers(0, n, 4000)])  # every node has an out-edge
+    col = rng.integers(0, n, row.size)
+    return cases.csr_of(row, col, n) + (n,)
+
+
+def test_one_type_equals_the_first_order_walk():
+    indptr, indices, n = no_dead_end_graph()
+    start = torch.arange(n).repeat(3)
+    for length in (1, 9, 40):
+        want = random_walk(indptr, indices, start, length, restart_p=0.0, seed=77)
+        got, lengths = metapath_walk(indptr, indices, torch.zeros(n, dtype=torch.long), start, "0-0", length, seed=77,
+                                     return_lengths=True)
+        assert torch.equal(got, want) and bool((lengths == length).all())
+        assert torch.equal(metapath_walk(indptr, indices, torch.zeros(n, dtype=torch.int32), start, [[0, 0, 0]], length, seed=77), want)
+
+
+# ---------------------------------------------------------------------------------------------------- typed_rows
+@pytest.mark.parametrize("name", sorted(cases.CASES))
+def test_typed_rows_layout(name):
+    indptr, indices, node_type, n = cases.CASES[name]()
+    t = int(node_type.max()) + 1
+    seg, indices_t = typed_rows(indptr, indices, node_type)
+    assert seg.dtype == torch.int64 and tuple(seg.shape) == (n * t + 1,) and indices_t.dtype == torch.int64
+    assert torch.equal(seg[::t], indptr) and int(seg[n * t]) == indices.numel()
+    assert bool((seg[1:] >= seg[:-1]).all())
+    ip, ix, ty, sg, it = indptr.numpy(), indices.numpy(), node_type.numpy(), seg.numpy(), indices_t.numpy()
+    for v in range(n):
+        nb = ix[ip[v]:ip[v + 1]]
+        for c in range(t):
+            want = nb[ty[nb] == c]  # the neighbours of type c in their original order: stable
+            assert np.array_equal(it[sg[v * t + c]:sg[v * t + c + 1]], want), (v, c)
+    wider, _ = typed_rows(indptr, indices, node_type, num_types=t + 2)  # empty segments for the absent types
+    assert tuple(wider.shape) == (n * (t + 2) + 1,) and torch.equal(wider[::t + 2], indptr)
+    assert torch.equal(typed_rows(indptr, indices, node_type.int())[1], indices_t)
+
+
+def test_typed_rows_with_one_type_is_the_input_itself():
+    indptr, indices, node_type, n = cases.random_typed()
+    zeros = torch.zeros(n, dtype=torch.long)
+    seg, indices_t = typed_rows(indptr, indices, zeros)
+    assert seg is indptr and indices_t is indices
+    seg, indices_t = typed_rows(indptr, indices, zeros, num_types=1)
+    assert seg is indptr and indices_t is indices
+
+
+def test_typed_rows_cache_hits_and_misses():
+    indptr, indices, node_type, n = cases.random_typed()
+    seg, indices_t = typed_rows(indptr, indices, node_type)
+    again = typed_rows(indptr, indices, node_type)
+    assert again[0] is seg and again[1] is indices_t
+    other = typed_rows(indptr, indices, node_type.clone())  # node_type is part of the key
+    assert other[0] is not seg and torch.equal(other[0], seg)
+    assert typed_rows(indptr, indices, node_type)[0] is seg
+    a = int(indices[0])
+    b = int(torch.nonzero(node_type != node_type[a])[0])  # a node of another type: the edit below changes the layout
+    indices[0] = b  # in place: the version counter moves
+    edited = typed_rows(indptr, indices, node_type)
+    assert edited[0] is not seg and not torch.equal(edited[0], seg)
+    node_type[b] = int(node_type[a])
+    last = typed_rows(indptr, indices, node_type)
+    assert last[0] is not edited[0] and not torch.equal(last[0], edited[0])
+
+
+# ---------------------------------------------------------------------------------------------------- determinism
+def test_seed_determinism_and_independence_of_batching():
+    indptr, indices, node_type, n = cases.random_typed()
+    schema = "0-1-0,0-2-0,1-0-2-0-1"
+    start, which = cases.starts_for(node_type, walk_mod.parse_schema(schema), repeat=20)
+    a = metapath_walk(indptr, indices, node_type, start, schema, 16, walker_path=which, seed=123)
+    assert torch.equal(a, metapath_walk(indptr, indices, node_type, start, schema, 16, walker_path=which, seed=123))
+    assert not torch.equal(a, metapath_walk(indptr, indices, node_type, start, schema, 16, walker_path=which, seed=124))
+    assert torch.equal(metapath_walk(indptr, indices, node_type, start[:777], schema, 16, walker_path=which[:777], seed=123), a[:777])
+    other = start.clone()
+    other[1::2] = start[1]  # (the same metapath has to fit: walker 1's start, given to the odd walkers of its metapath only)
+    keep = which == which[1]
+    other = torch.where(keep, other, start)
+    b = metapath_walk(indptr, indices, node_type, other, schema, 16, walker_path=which, seed=123)
+    assert torch.equal(b[0::2], a[0::2])
+
+
+def test_seed_none_follows_torch_manual_seed():
+    indptr, indices, node_type, n = cases.random_typed()
+    start, which = cases.starts_for(node_type, [[0, 1, 0]], repeat=4)
+    torch.manual_seed(7)
+    a1, a2 = (metapath_walk(indptr, indices, node_type, start, "0-1-0", 10) for _ in range(2))
+    torch.manual_seed(7)
+    b1 = metapath_walk(indptr, indices, node_type, start, "0-1-0", 10)
+    assert torch.equal(a1, b1) and not torch.equal(a1, a2)
+
+
+def test_result_does_not_depend_on_the_number_of_openmp_threads():
+    code = r'''
+import hashlib, sys
+sys.path[:0] = [sys.argv[1], sys.argv[1] + "/tests"]
+import numpy as np, torch
+from cogdl_amd.operators import metapath_walk
+rng = np.random.default_rng(1)
+n = 2000
+row = np.sort(rng.integers(0, n, 30000)); col = rng.integers(0, n, 30000)
+indptr = np.zeros(n + 1, dtype=np.int64); np.cumsum(np.bincount(row, minlength=n), out=indptr[1:])
+indptr, indices = torch.from_numpy(indptr), torch.from_numpy(col)
+types = torch.from_numpy(rng.integers(0, 3, n))
+start = torch.nonzero(types == 0).flatten().repeat(8)
+a, l = metapath_walk(indptr, indices, types, start, "0-1-0-2-0", 40, seed=5, return_lengths=True)
+assert start.numel() * 40 >= 4096 and int(l.min()) < 40 < int(l.sum())
+from cogdl_amd import _lib
+assert _lib._hip is None, "a CPU graph loaded libcogdl_hip.so"
+print(hashlib.sha256(a.numpy().tobytes() + l.numpy().tobytes()).hexdigest())
+'''
+    digests = []
+    for threads in ("1", "4"):
+        out = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True,
+                             env=dict(os.environ, OMP_NUM_THREADS=threads))
+        assert out.returncode == 0, out.stderr[-2000:]
+        digests.append(out.stdout.strip())
+    assert digests[0] == digests[1] and len(digests[0]) == 64
+
+
+# ---------------------------------------------------------------------------------------------------- the law of the draw
+def law_graph():
+    """Node 0 (type 0) -> type-1 nodes 1..6 with multiplicities 1 2 3 1 1 5 and type-2 nodes 7..9 with 2 1 1, interleaved.
+    Type-1 nodes -> type-2 nodes with various multiplicities (node 4 has none: its walk ends there) and back to 0."""
+    types = [0] + [1] * 6 + [2] * 3
+    row, col = [], []
+    for v, m in zip(range(1, 10), (1, 2, 3, 1, 1, 5, 2, 1, 1)):
+        row += [0] * m
+        col += [v] * m
+    order = np.random.default_rng(3).permutation(len(row))
+    row, col = list(np.asarray(row)[order]), list(np.asarray(col)[order])
+    second = {1: [7, 7, 8], 2: [9], 3: [7, 8, 9, 9], 4: [], 5: [8, 8, 8, 7], 6: [9, 7]}
+    for v, nb in second.items():
+        for x in nb:
+            row += [v, v]
+            col += [x, 0]  # a type-0 neighbour in between: never taken when type 2 is wanted
+        row.append(v)
+        col.append(0)
+    for v in (7, 8, 9):
+        row.append(v)
+        col.append(0)
+    return cases._case(row, col, types)
+
+
+def typed_transition(indptr, indices, node_type, t):
+    """P[v, x] = (multiplicity of v -> x) / (number of entries of type t in row v) for x of type t; a row without such an
+    entry puts its mass on the extra column n: the walk ends."""
+    ip, ix, ty = indptr.numpy(), indices.numpy(), node_type.numpy()
+    n = ip.size - 1
+    p = np.zeros((n + 1, n + 1))
+    for v in range(n):
+        nb = ix[ip[v]:ip[v + 1]]
+        nb = nb[ty[nb] == t]
+        if nb.size:
+            np.add.at(p[v], nb, 1.0 / nb.size)
+        else:
+            p[v, n] = 1.0
+    p[n, n] = 1.0
+    return p
+
+
+def assert_chi_square(counts, prob, what):
+    counts, prob = np.asarray(counts, dtype=np.float64), np.asarray(prob, dtype=np.float64)
+    support = prob > 0
+    assert counts[~support].sum() == 0, "%s: samples outside the support" % what
+    total = counts.sum()
+    expected = prob[support] * total
+    stat = float(((counts[support] - expected) ** 2 / expected).sum())
+    bound = float(chi2.ppf(QUANTILE, int(support.sum()) - 1))
+    print("%s: chi-square %.1f, bound %.1f (%d cells, %d samples)" % (what, stat, bound, int(support.sum()), int(total)))
+    assert stat <= bound, "%s: chi-square %.1f above the 1 - 1e-6 quantile %.1f" % (what, stat, bound)
+
+
+@pytest.mark.parametrize("wanted", [1, 2])
+def test_single_step_follows_the_law_with_multiplicity(wanted):
+    indptr, indices, node_type, n = law_graph()
+    start = torch.zeros(500_000, dtype=torch.long)
+    nxt = metapath_walk(indptr, indices, node_type, start, [[0, wanted, 0]], 2, seed=1000 + wanted)[:, 1].numpy()
+    law = typed_transition(indptr, indices, node_type, wanted)[0]
+    assert int((law > 0).sum()) == (6 if wanted == 1 else 3)
+    assert_chi_square(np.bincount(np.where(nxt < 0, n, nxt), minlength=n + 1), law, "one step to type %d" % wanted)
+
+
+def test_two_steps_follow_the_typed_transition_matrices():
+    indptr, indices, node_type, n = law_graph()
+    start = torch.zeros(500_000, dtype=torch.long)
+    walks = metapath_walk(indptr, indices, node_type, start, "0-1-2-0", 3, seed=2000).numpy()
+    law = typed_transition(indptr, indices, node_type, 1)[0] @ typed_transition(indptr, indices, node_type, 2)
+    assert law[n] > 0  # (through node 4 the walk ends: -1 is a cell of the law)
+    third = walks[:, 2]
+    assert_chi_square(np.bincount(np.where(third < 0, n, third), minlength=n + 1), law, "two steps, types 1 then 2")
+
+
+# ---------------------------------------------------------------------------------------------------- errors
+def test_bad_schemas_raise_before_anything_runs():
+    indptr, indices, node_type, n = cases.random_typed()
+    start = torch.nonzero(node_type == 0).flatten()
+    for bad in ("0-1", "0", "", "a-b-a", "0-1.5-0", "0-1-0,", [[0]], [[0, 1]], [], [[0, 1.5, 0]]):
+        with pytest.raises(ValueError):
+            metapath_walk(indptr, indices, node_type, start, bad, 5, seed=0)
+    with pytest.raises(ValueError):
+        metapath_walk(indptr, indices, node_type, start, "0-1-0,0-2-0", 5, seed=0)  # two metapaths, no walker_path
+    for outside in ("0-3-0", "0--1-0", [[0, 64, 0]]):
+        with pytest.raises(ValueError):
+            metapath_walk(indptr, indices, node_type, start, outside, 5, seed=0)
+    with pytest.raises(ValueError):
+        metapath_walk(indptr, indices, node_type, start, "0-1-0", 0, seed=0)
+    with pytest.raises(_lib.BackendError):
+        metapath_walk(indptr, indices, node_type, start, "0-1-0", 5, walker_path=torch.zeros(3, dtype=torch.int32), seed=0)
+    with pytest.raises(_lib.BackendError):
+        metapath_walk(indptr, indices, node_type.float(), start, "0-1-0", 5, seed=0)
+
+
+def test_typed_rows_refuses_bad_layout_arguments():
+    indptr, indices, node_type, n = cases.random_typed()
+    with pytest.raises(_lib.BackendError):
+        typed_rows(indptr, indices, node_type, num_types=65)
+    with pytest.raises(_lib.BackendError):
+        typed_rows(indptr, indices, node_type, num_types=0)
+    with pytest.raises(_lib.BackendError):
+        typed_rows(indptr, indices, node_type, num_types=2)  # a type outside [0, 2)
+    many = node_type.clone()
+    many[5] = 64  # T = 65
+    with pytest.raises(_lib.BackendError):
+        metapath_walk(indptr, indices, many, torch.tensor([0]), "0-0", 4, seed=0)
+    negative = node_type.clone()
+    negative[5] = -1
+    with pytest.raises(_lib.BackendError):
+        typed_rows(indptr, indices, negative)
+    with pytest.raises(_lib.BackendError):
+        typed_rows(indptr, indices, node_type[:-1])
+    broken = indptr.clone()
+    broken[3] = broken[4] + 1
+    with pytest.raises(_lib.BackendError):
+        typed_rows(broken, indices, node_type)
+    with pytest.raises(_lib.BackendError):
+        typed_rows(indptr, indices[:-1], node_type)  # indptr[-1] != E
+    bad = indices.clone()
+    bad[7] = n
+    with pytest.raises(_lib.BackendError):
+        typed_rows(indptr, bad, node_type)
+    with pytest.raises(_lib.BackendError):
+        typed_rows(indptr.int(), indices, node_type)
+
+
+def host_call(seg, indices_t, n, t, types, start, which, length, pattern, path_off, lengths=True):
+    """The host entry point itself -> (rc, flags, walks, lengths)."""
+    start, which = torch.as_tensor(start, dtype=torch.long), torch.as_tensor(which, dtype=torch.int32)
+    pattern, path_off = torch.as_tensor(pattern, dtype=torch.int32), torch.as_tensor(path_off, dtype=torch.int32)
+    w = start.numel()
+    walks = torch.full((w, length), -7, dtype=torch.long)
+    held = torch.full((w,), -7, dtype=torch.int32) if lengths else None
+    flags = torch.full((1,), -7, dtype=torch.int32)
+    rc = _lib.host().cogdl_host_metapath_walk(_lib.ptr(seg), _lib.ptr(indices_t), n, t, indices_t.numel(), _lib.ptr(types),
+                                              _lib.ptr(start), _lib.ptr(which), w, length, _lib.ptr(pattern), _lib.ptr(path_off),
+                                              path_off.numel() - 1, 9, _lib.ptr(walks), _lib.ptr(held), _lib.ptr(flags))
+    return rc, int(flags), walks, held
+
+
+def test_flags_of_the_host_entry_point():
+    indptr, indices, node_type, n = cases.random_typed()
+    seg, indices_t = typed_rows(indptr, indices, node_type)
+    types = node_type.int()
+    zero, one = int(torch.nonzero(node_type == 0)[0]), int(torch.nonzero(node_type == 1)[0])
+    rc, flags, walks, held = host_call(seg, indices_t, n, 3, types, [zero, zero], [0, 0], 9, [0, 1], [0, 2])
+    assert (rc, flags) == (0, 0) and int(walks.min()) >= -1
+    # a start node of the wrong type: flag 8, position 0 holds the start, the rest -1; without node_type nothing is checked
+    rc, flags, walks, held = host_call(seg, indices_t, n, 3, types, [zero, one], [0, 0], 9, [0, 1], [0, 2])
+    assert (rc, flags) == (0, 8) and walks[1].tolist() == [one] + [-1] * 8 and held.tolist()[1] == 1
+    rc, flags, _, _ = host_call(seg, indices_t, n, 3, None, [zero, one], [0, 0], 9, [0, 1], [0, 2])
+    assert (rc, flags) == (0, 0)
+    with pytest.raises(_lib.BackendError, match="first type of its metapath"):
+        metapath_walk(indptr, indices, node_type, torch.tensor([zero, one]), "0-1-0", 9, seed=0)
+    # a start id out of range: flag 1
+    for bad in (n, -3):
+        rc, flags, walks, _ = host_call(seg, indices_t, n, 3, types, [zero, bad], [0, 0], 9, [0, 1], [0, 2])
+        assert (rc, flags) == (0, 1) and walks[1].tolist() == [bad] + [-1] * 8
+        with pytest.raises(_lib.BackendError, match="start id"):
+            metapath_walk(indptr, indices, node_type, torch.tensor([zero, bad]), "0-1-0", 9, seed=0)
+    # a wanted type outside [0, T), a metapath id outside [0, n_paths), a malformed path_off: flag 16
+    assert host_call(seg, indices_t, n, 3, types, [zero], [0], 9, [0, 3], [0, 2])[1] == 16
+    assert host_call(seg, indices_t, n, 3, types, [zero], [1], 9, [0, 1], [0, 2])[1] == 16
+    assert host_call(seg, indices_t, n, 3, types, [zero], [-1], 9, [0, 1], [0, 2])[1] == 16
+    assert host_call(seg, indices_t, n, 3, types, [zero, zero], [0, 1], 9, [0, 1], [0, 2, 2])[1] == 16
+    # a tampered seg: flag 4, nothing is read out of bounds
+    busy = int(torch.nonzero((seg[1:] - seg[:-1])[::3] > 0)[0])  # a node with type-0 neighbours... of any type: start there
+    for value in (1 << 40, -5):
+        tampered = seg.clone()
+        tampered[busy * 3 + 1] = value
+        starts = torch.full((64,), busy, dtype=torch.long)
+        rc, flags, walks, _ = host_call(tampered, indices_t, n, 3, None, starts, [0] * 64, 9, [0, 0, 1, 2], [0, 4])
+        assert rc == 0 and flags & 4 and int(walks.min()) >= -1 and int(walks.max()) < n
+    # argument checks
+    lib = _lib.host()
+    args = lambda t, paths, wp: (_lib.ptr(seg), _lib.ptr(indices_t), n, t, indices_t.numel(), None, _lib.ptr(seg), wp, 1, 4,  # noqa: E731
+                                 _lib.ptr(seg), _lib.ptr(seg), paths, 1, _lib.ptr(seg), None, _lib.ptr(seg))
+    assert lib.cogdl_host_metapath_walk(*args(0, 1, _lib.ptr(seg))) == 1
+    assert lib.cogdl_host_metapath_walk(*args(65, 1, _lib.ptr(seg))) == 1
+    assert lib.cogdl_host_metapath_walk(*args(3, 0, _lib.ptr(seg))) == 1
+    assert lib.cogdl_host_metapath_walk(*args(3, 1, None)) == 1
+
+
+def test_no_walkers_and_length_one():
+    indptr, indices, node_type, n = cases.random_typed()
+    empty, held = metapath_walk(indptr, indices, node_type, torch.empty(0, dtype=torch.long), "0-1-0", 7, seed=0, return_lengths=True)
+    assert tuple(empty.shape) == (0, 7) and tuple(held.shape) == (0,)
+    start = torch.nonzero(node_type == 1).flatten()
+    one, held = metapath_walk(indptr, indices, node_type, start, "1-2-1", 1, seed=0, return_lengths=True)
+    assert torch.equal(one[:, 0], start) and held.tolist() == [1] * start.numel()
+
+
+# ---------------------------------------------------------------------------------------------------- the reference's walk
+def test_corridor_walks_equal_the_reference_record():
+    z = np.load(GOLDEN)
+    indptr, indices, node_type, n = cases.corridor()
+    row = np.repeat(np.arange(n), np.diff(indptr.numpy()))
+    assert np.array_equal(z["row"], row) and np.array_equal(z["col"], indices.numpy())  # the record is of THIS graph
+    assert np.array_equal(z["node_type"], node_type.numpy())
+    ip, ix, ty = indptr.numpy(), indices.numpy(), node_type.numpy()
+    for v in range(n):  # at most one neighbour of each type: the walk cannot depend on the draws
+        assert np.bincount(ty[ix[ip[v]:ip[v + 1]]], minlength=3).max() <= 1
+    length = int(z["length"])
+    early = 0
+    for k, schema in enumerate(cases.CORRIDOR_SCHEMAS):
+        assert bytes(z["schema_%d" % k]).decode() == schema
+        start, want = torch.from_numpy(z["start_%d" % k]), z["walks_%d" % k]
+        got, held = metapath_walk(indptr, indices, node_type, start, schema, length, seed=k, return_lengths=True)
+        assert np.array_equal(got.numpy(), want), schema
+        assert np.array_equal(held.numpy(), (want >= 0).sum(1))
+        early += int((want[:, -1] < 0).sum())
+        assert int((want[:, -1] >= 0).sum()) > 0, "no walk of %s reaches the full length" % schema
+    assert early > 10
