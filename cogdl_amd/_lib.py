@@ -347,6 +347,29 @@ def check_host(rc, what):
         raise BackendError("%s failed: %s" % (what, host().cogdl_host_strerror(rc).decode()))
 
 
+# name -> the twin's function in each library, resolved once per name (twin_call runs in front of every launch).  The entries
+# stay valid only because hip() and host() load their library once and never replace it.
+_HIP_TWIN, _HOST_TWIN = {}, {}
+
+
+def twin_call(name, dev, *args):
+    """An operator that has a twin in each library, for tensors on device `dev`: cogdl_hip_<name>(*args, current stream) on
+    a CUDA device, cogdl_host_<name>(*args) otherwise; a non-zero status raises BackendError.  Only the library that is
+    called gets loaded: a CPU graph never loads libcogdl_hip.so."""
+    if dev.type == "cuda":
+        fn = _HIP_TWIN.get(name)
+        if fn is None:
+            fn = _HIP_TWIN[name] = getattr(hip(), "cogdl_hip_" + name)
+        with on_device(dev):
+            rc = fn(*args, _raw_stream(dev.index))
+        check(rc, name)
+    else:
+        fn = _HOST_TWIN.get(name)
+        if fn is None:
+            fn = _HOST_TWIN[name] = getattr(host(), "cogdl_host_" + name)
+        check_host(fn(*args), name)
+
+
 def require_cuda(*tensors):
     dev = None
     for t in tensors:

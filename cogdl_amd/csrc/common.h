@@ -44,6 +44,24 @@ inline hipError_t fill_u32_async(void *p, uint32_t v, size_t n_words, hipStream_
     return hipGetLastError();
 }
 
+// An operator's error flags word (one int in device memory).  Zeroed on the stream in front of the operator's kernels...
+inline int clear_flags_async(int *flags, hipStream_t s) {
+    const hipError_t e = fill_u32_async(flags, 0u, 1, s);
+    if (e != hipSuccess) {
+        g_last_hip_error = (int)e;
+        return COGDL_HIP_ELAUNCH;
+    }
+    return COGDL_HIP_OK;
+}
+// ... and raised by a plain read-or-write, no atomics: concurrent writers of DIFFERENT bits may lose one of them, never the
+// fact that the word is non-zero; the result is invalid either way.
+__device__ __forceinline__ void raise_flags(int *flags, int err) {
+    if (err) {
+        volatile int *f = flags;
+        *f = *f | err;
+    }
+}
+
 // Run-time tuning knobs (cogdl_hip_set_tuning): experiments without recompiling.
 enum Tuning { kTuneXcdStripe = 0, kTuneLongThresh = 1, kTuneRowSort = 2, kTuneLongGrid = 3, kTuneGatVec = 4, kTuneGatOnline = 5, kTuneSpmmVec = 6, kTuneEsScalar = 7, kTuneEsSpin = 8, kTuneEsDebug = 9, kTuneCsr2csc = 10, kTuneSampleRelabel = 11, kTuneWaveSplit = 12, kTuneRowDebug = 13, kTuneRowTile = 14, kTuneSegmentEdges = 15, kTuneRowQueue = 16, kTuneSgnsVariant = 17, kTuneSweepRows = 18, kTuneCount = 19 };
 extern int g_tuning[kTuneCount];

@@ -415,16 +415,27 @@ int cogdl_host_csr_spmm_f32_i64(const int64_t *rowptr, const int32_t *colind, co
 }  // extern "C"
 
 // ---------------------------------------------------------------- random walks (the twin of csrc/walk.hip)
-// The draws and the rules of a step are walk_draw.h's, the same functions the kernels run: equal arrays for equal inputs.
+// A walk kind is a rule of walk_draw.h, the same code the kernel runs: equal arrays for equal inputs.  Here: the loop that
+// runs a rule over one walker's row, and entry points that check their own parameters and spread the walkers over OpenMP.
 namespace {
 namespace wk = cogdl_walk;
 
-int walk_args_status(const int64_t *indptr, const int64_t *indices, int64_t num_nodes, int64_t num_edges,
-                     const int64_t *start, int64_t n_walkers, int64_t length, const int64_t *walks, const int *flags) {
-    if (num_nodes < 0 || num_edges < 0 || n_walkers < 0 || length < 1 || length > 0x7fffffff || !flags) return COGDL_HOST_EINVAL;
-    if (n_walkers > 0 && (!indptr || !start || !walks)) return COGDL_HOST_EINVAL;
-    if (num_edges > 0 && !indices) return COGDL_HOST_EINVAL;
-    return COGDL_HOST_OK;
+// (every refusal is EINVAL here, a length above 2^31 - 1 included: walk_draw.h has the differences between the libraries)
+int walk_args_rc(const int64_t *indptr, const int64_t *indices, int64_t num_nodes, int64_t num_edges, const int64_t *start,
+                 int64_t n_walkers, int64_t length, const int64_t *walks, const int *flags) {
+    const int rc = wk::walk_args_status(indptr, indices, num_nodes, num_edges, start, n_walkers, length, walks, flags, INT64_MAX);
+    return rc == wk::kArgsOk ? COGDL_HOST_OK : COGDL_HOST_EINVAL;
+}
+
+// Walker w from begin to finish into its row -> its error bits.
+template <class Rule>
+inline int walk_row(const Rule &rule, uint64_t seed, int64_t w, int64_t length, int64_t *out) {
+    typename Rule::State st = {};
+    int err = 0;
+    out[0] = rule.begin(st, w, err);
+    for (int64_t i = 1; i < length; ++i) out[i] = rule.advance(st, seed, w, i, err);
+    rule.finish(st, w);
+    return err;
 }
 }  // namespace
 
@@ -433,22 +444,13 @@ extern "C" {
 int cogdl_host_random_walk(const int64_t *indptr, const int64_t *indices, int64_t num_nodes, int64_t num_edges,
                            const int64_t *start, int64_t n_walkers, int64_t length, double restart_p, uint64_t seed,
                            int64_t *walks, int *flags) {
-    const int rc = walk_args_status(indptr, indices, num_nodes, num_edges, start, n_walkers, length, walks, flags);
+    const int rc = walk_args_rc(indptr, indices, num_nodes, num_edges, start, n_walkers, length, walks, flags);
     if (rc != COGDL_HOST_OK) return rc;
     if (!(restart_p >= 0.0 && restart_p <= 1.0)) return COGDL_HOST_EINVAL;
-    const wk::Graph g = {indptr, indices, num_nodes, num_edges};
-    const uint64_t restart_t = wk::fixed32(restart_p);
+    const wk::FirstOrderRule rule = {{indptr, indices, num_nodes, num_edges}, start, wk::fixed32(restart_p)};
     int all = 0;
 #pragma omp parallel for schedule(static) reduction(| : all) if (n_walkers * length >= 4096)
-    for (int64_t w = 0; w < n_walkers; ++w) {
-        int64_t *out = walks + w * length;
-        const int64_t first = start[w];
-        int64_t cur = first;
-        int err = wk::valid_id(g, cur) ? 0 : wk::kBadStart;
-        out[0] = cur;
-        for (int64_t i = 1; i < length; ++i) out[i] = cur = wk::step_first_order(g, seed, w, i, first, cur, restart_t, err);
-        all |= err;
-    }
+    for (int64_t w = 0; w < n_walkers; ++w) all |= walk_row(rule, seed, w, length, walks + w * length);
     *flags = all;
     return COGDL_HOST_OK;
 }
@@ -456,30 +458,14 @@ int cogdl_host_random_walk(const int64_t *indptr, const int64_t *indices, int64_
 int cogdl_host_node2vec_walk(const int64_t *indptr, const int64_t *indices, int64_t num_nodes, int64_t num_edges,
                              const int64_t *start, int64_t n_walkers, int64_t length, double p, double q, int max_trials,
                              uint64_t seed, int64_t *walks, int32_t *fallback_steps, int *flags) {
-    const int rc = walk_args_status(indptr, indices, num_nodes, num_edges, start, n_walkers, length, walks, flags);
+    const int rc = walk_args_rc(indptr, indices, num_nodes, num_edges, start, n_walkers, length, walks, flags);
     if (rc != COGDL_HOST_OK) return rc;
     if (!(p > 0.0) || !(q > 0.0) || !(p < 1e300) || !(q < 1e300) || max_trials < 0 || max_trials > (1 << 20)) return COGDL_HOST_EINVAL;
-    if (max_trials == 0) max_trials = wk::kDefaultTrials;
-    const wk::Graph g = {indptr, indices, num_nodes, num_edges};
-    const wk::N2vWeights wt = wk::n2v_weights(p, q);
+    const wk::Node2vecRule rule = {{indptr, indices, num_nodes, num_edges}, start, wk::n2v_weights(p, q),
+                                   max_trials == 0 ? wk::kDefaultTrials : max_trials, fallback_steps};
     int all = 0;
 #pragma omp parallel for schedule(dynamic, 64) reduction(| : all) if (n_walkers * length >= 4096)
-    for (int64_t w = 0; w < n_walkers; ++w) {
-        int64_t *out = walks + w * length;
-        int64_t prev = start[w], cur = prev;
-        int err = wk::valid_id(g, cur) ? 0 : wk::kBadStart;
-        int32_t n_fallback = 0;
-        out[0] = cur;
-        for (int64_t i = 1; i < length; ++i) {
-            bool fell_back;
-            const int64_t nxt = wk::step_node2vec(g, seed, w, i, prev, cur, wt, max_trials, err, fell_back);
-            n_fallback += fell_back ? 1 : 0;
-            prev = cur;
-            out[i] = cur = nxt;
-        }
-        if (fallback_steps) fallback_steps[w] = n_fallback;
-        all |= err;
-    }
+    for (int64_t w = 0; w < n_walkers; ++w) all |= walk_row(rule, seed, w, length, walks + w * length);
     *flags = all;
     return COGDL_HOST_OK;
 }
@@ -488,35 +474,16 @@ int cogdl_host_metapath_walk(const int64_t *seg, const int64_t *indices_t, int64
                              int64_t num_edges, const int32_t *node_type, const int64_t *start, const int32_t *walker_path,
                              int64_t n_walkers, int64_t length, const int32_t *pattern, const int32_t *path_off,
                              int32_t n_paths, uint64_t seed, int64_t *walks, int32_t *lengths, int *flags) {
-    const int rc = walk_args_status(seg, indices_t, num_nodes, num_edges, start, n_walkers, length, walks, flags);
+    const int rc = walk_args_rc(seg, indices_t, num_nodes, num_edges, start, n_walkers, length, walks, flags);
     if (rc != COGDL_HOST_OK) return rc;
     if (num_types < 1 || num_types > 64 || n_paths < 1) return COGDL_HOST_EINVAL;
     if (n_walkers > 0 && (!walker_path || !pattern || !path_off)) return COGDL_HOST_EINVAL;
     if (num_nodes > ((int64_t)1 << 56)) return COGDL_HOST_ERANGE;
-    const wk::TypedGraph g = {seg, indices_t, num_nodes, num_edges, num_types};
+    const wk::MetapathRule rule = {{seg, indices_t, num_nodes, num_edges, num_types}, node_type, start, walker_path, pattern,
+                                   path_off, n_paths, lengths};
     int all = 0;
 #pragma omp parallel for schedule(static) reduction(| : all) if (n_walkers * length >= 4096)
-    for (int64_t w = 0; w < n_walkers; ++w) {
-        int64_t *out = walks + w * length;
-        int err = 0;
-        const int64_t first = start[w];
-        wk::PathCursor pc = wk::metapath_begin(g, node_type, first, walker_path[w], pattern, path_off, n_paths, err);
-        int64_t cur = err ? -1 : first;
-        int32_t n_held = 1;
-        out[0] = first;
-        for (int64_t i = 1; i < length; ++i) {
-            if (err == 0 && cur >= 0) {
-                const int32_t t = wk::metapath_next_type(pc);
-                cur = wk::step_metapath(g, t, seed, w, i, cur, err);
-                n_held += cur >= 0 ? 1 : 0;
-            } else {
-                cur = -1;
-            }
-            out[i] = cur;
-        }
-        if (lengths) lengths[w] = n_held;
-        all |= err;
-    }
+    for (int64_t w = 0; w < n_walkers; ++w) all |= walk_row(rule, seed, w, length, walks + w * length);
     *flags = all;
     return COGDL_HOST_OK;
 }

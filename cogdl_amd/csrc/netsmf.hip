@@ -13,7 +13,7 @@
 // take consecutive entries e, so the reads of indices[e] and both stores are coalesced; no LDS staging is needed.
 // No LDS and a register count that admits 8 waves per SIMD (34 VGPRs), blocks of 256: the
 // occupancy a latency-bound gather wants.  The grid is a fixed number of blocks per CU striding over the pairs.
-// Error flags are raised as in walk.hip: a plain read-or-write of the flags word, never losing the fact that it is non-zero.
+// Error flags are raised as in walk.hip, with raise_flags (common.h).
 #include "common.h"
 
 #include "netsmf_law.h"
@@ -37,10 +37,7 @@ __global__ __launch_bounds__(kNetsmfBlock) void netsmf_sample_kernel(cogdl_walk:
         out_row[j] = p.u;
         out_col[j] = p.v;
     }
-    if (err) {
-        volatile int *f = flags;
-        *f = *f | err;
-    }
+    raise_flags(flags, err);
 }
 
 }  // namespace cogdl
@@ -53,12 +50,8 @@ extern "C" int cogdl_hip_netsmf_sample(const int64_t *indptr, const int64_t *ind
     const int rc = ns::args_status(indptr, indices, num_nodes, num_edges, first_sample, n_samples, window, out_row, out_col, flags);
     if (rc != ns::kArgsOk) return rc == ns::kArgsRange ? COGDL_HIP_ERANGE : COGDL_HIP_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    const hipError_t e = fill_u32_async(flags, 0u, 1, s);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return COGDL_HIP_ELAUNCH;
-    }
-    if (n_samples == 0) return COGDL_HIP_OK;
+    const int cleared = clear_flags_async(flags, s);
+    if (cleared != COGDL_HIP_OK || n_samples == 0) return cleared;
     const cogdl_walk::Graph g = {indptr, indices, num_nodes, num_edges};
     const int64_t total = n_samples * window;
     int64_t blocks = (total + kNetsmfBlock - 1) / kNetsmfBlock;

@@ -169,10 +169,7 @@ __global__ void sgns_check_kernel(const int64_t *__restrict__ walks, int64_t n_t
         if (v > 0 && cum[v] < cum[v - 1]) err |= sg::kBadTable;
         if (v == V - 1 && cum[v] == 0) err |= sg::kBadTable;
     }
-    if (err) {  // (plain read-or-write as in walk.hip: a bit may be lost to a concurrent writer, never the non-zero word)
-        volatile int *f = flags;
-        *f = *f | err;
-    }
+    raise_flags(flags, err);
 }
 
 __global__ void sgns_init_kernel(float *__restrict__ syn0, float *__restrict__ syn1, int64_t V, int D, uint64_t seed) {
@@ -219,11 +216,8 @@ extern "C" int cogdl_hip_sgns_train(const int64_t *walks, int64_t W, int64_t L, 
     if (!keep || !cum || !exp_table || !syn0 || !syn1 || !flags || (W > 0 && !walks) || workers < 0 || rows_in_flight < 0)
         return COGDL_HIP_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    const hipError_t e = fill_u32_async(flags, 0u, 1, s);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return COGDL_HIP_ELAUNCH;
-    }
+    const int cleared = clear_flags_async(flags, s);
+    if (cleared != COGDL_HIP_OK) return cleared;
     const int64_t n_check = std::max<int64_t>(W * L, V);
     hipLaunchKernelGGL(sgns_check_kernel, dim3((unsigned)std::min<int64_t>((n_check + 255) / 256, 8192)), dim3(256), 0, s, walks,
                        W * L, cum, V, flags);

@@ -1,7 +1,10 @@
-// walk_draw.h -- the random draws and the per-step rules of the random walks, shared by the HIP kernels (walk.hip)
-// and their host twin (host_ops.cpp).  Plain C++: no HIP runtime, no libc beyond <stdint.h>; libcogdl_host.so includes
-// it and must stay HIP-free.  Because both sides run the SAME functions on the same integers, a walk is the same array
-// on the GPU and on the host, bit for bit.
+// walk_draw.h -- the random draws, the step functions and the RULE of every kind of random walk, shared by the HIP kernel
+// (walk.hip) and its host twin (host_ops.cpp).  Plain C++: no HIP runtime, no libc beyond <stdint.h>; libcogdl_host.so
+// includes it and must stay HIP-free.  A rule (FirstOrderRule, Node2vecRule, MetapathRule, at the end of this file) is
+// everything a walk kind decides: what a walker carries, what position 0 holds, how it advances, when it counts and what
+// it stores at the end.  Each side owns only a scaffold that runs a rule (the tile loop of walk_kernel, the row loop of
+// host_ops.cpp), so both run the SAME code on the same integers: a walk is the same array on the GPU and on the host,
+// bit for bit.  The argument check of the entry points is here too (walk_args_status).
 //
 // Randomness.  Every draw is a pure function of (seed, walker w, step i, trial) through Philox4x32-10 (Salmon et al.,
 // SC'11; the round function is restated here because philox.h pulls in the HIP runtime):
@@ -285,6 +288,122 @@ COGDL_WALK_FN int64_t step_metapath(const TypedGraph &g, int32_t t, uint64_t see
         return -1;
     }
     return x;
+}
+
+// ---------------------------------------------------------------- the rules
+// A rule holds the constants of one call (passed by value to the kernel) and three functions over its per-walker State:
+//   begin(st, w, err)             walker w: validates, raises into err -> what position 0 holds
+//   advance(st, seed, w, i, err)  -> what position i >= 1 holds
+//   finish(st, w)                 stores the walker's side output where the call asked for one
+// A scaffold starts a walker with a zeroed State and err = 0 and calls advance for i = 1, 2, .. in order.  Once err is up
+// the step functions read nothing more.
+struct FirstOrderRule {
+    Graph g;
+    const int64_t *start;
+    uint64_t restart_t;
+    struct State {
+        int64_t first, cur;
+    };
+    COGDL_WALK_FN int64_t begin(State &st, int64_t w, int &err) const {
+        st.first = st.cur = start[w];
+        if (!valid_id(g, st.cur)) err |= kBadStart;
+        return st.cur;
+    }
+    COGDL_WALK_FN int64_t advance(State &st, uint64_t seed, int64_t w, int64_t i, int &err) const {
+        return st.cur = step_first_order(g, seed, w, i, st.first, st.cur, restart_t, err);
+    }
+    COGDL_WALK_FN void finish(const State &, int64_t) const {}
+};
+
+struct Node2vecRule {
+    Graph g;
+    const int64_t *start;
+    N2vWeights wt;
+    int max_trials;
+    int32_t *fallback_steps;  // [n_walkers] or null: steps that the exact pass decided
+    struct State {
+        int64_t prev, cur;
+        int32_t n_fallback;
+    };
+    COGDL_WALK_FN int64_t begin(State &st, int64_t w, int &err) const {
+        st.prev = st.cur = start[w];
+        st.n_fallback = 0;
+        if (!valid_id(g, st.cur)) err |= kBadStart;
+        return st.cur;
+    }
+    COGDL_WALK_FN int64_t advance(State &st, uint64_t seed, int64_t w, int64_t i, int &err) const {
+        bool fell_back;
+        const int64_t nxt = step_node2vec(g, seed, w, i, st.prev, st.cur, wt, max_trials, err, fell_back);
+        st.n_fallback += fell_back ? 1 : 0;
+        st.prev = st.cur;
+        return st.cur = nxt;
+    }
+    COGDL_WALK_FN void finish(const State &st, int64_t w) const {
+        if (fallback_steps) fallback_steps[w] = st.n_fallback;
+    }
+};
+
+// Position 0 holds the start id even where it is refused; after that a walker whose walk has ended, or that raised a flag,
+// holds -1 and reads nothing.  The wanted type does not depend on where the walker stands, so it is fetched one step ahead
+// (t_next): in the kernel that load (4 bytes of a table of a few dozen entries: an L1/L2 hit) is in flight together with the
+// two dependent loads of the step before it; on the host it is harmless.
+struct MetapathRule {
+    TypedGraph g;
+    const int32_t *node_type;
+    const int64_t *start;
+    const int32_t *walker_path, *pattern, *path_off;
+    int32_t n_paths;
+    int32_t *lengths;  // [n_walkers] or null: positions that hold a node
+    struct State {
+        int64_t cur;
+        PathCursor pc;
+        int32_t t_next, n_held;
+    };
+    COGDL_WALK_FN int64_t begin(State &st, int64_t w, int &err) const {
+        const int64_t first = start[w];
+        st.pc = metapath_begin(g, node_type, first, walker_path[w], pattern, path_off, n_paths, err);
+        st.n_held = 1;
+        st.cur = -1;
+        st.t_next = 0;
+        if (err == 0) {
+            st.cur = first;
+            st.t_next = metapath_next_type(st.pc);  // the type wanted at position 1
+        }
+        return first;
+    }
+    COGDL_WALK_FN int64_t advance(State &st, uint64_t seed, int64_t w, int64_t i, int &err) const {
+        if (err == 0 && st.cur >= 0) {
+            const int32_t t = st.t_next;
+            st.t_next = metapath_next_type(st.pc);
+            st.cur = step_metapath(g, t, seed, w, i, st.cur, err);
+            st.n_held += st.cur >= 0 ? 1 : 0;
+        } else {
+            st.cur = -1;
+        }
+        return st.cur;
+    }
+    COGDL_WALK_FN void finish(const State &st, int64_t w) const {
+        if (lengths) lengths[w] = st.n_held;
+    }
+};
+
+enum : int { kArgsOk = 0, kArgsInvalid = 1, kArgsRange = 2 };
+
+// The argument check of the walk entry points of both libraries (each maps the result to its own status codes; the typed
+// graph passes seg / indices_t as indptr / indices).  Where the libraries differ:
+//   * length > 2^31 - 1 (the step index is one 32-bit word of the Philox counter) is kArgsRange: libcogdl_hip answers
+//     ERANGE, libcogdl_host answers EINVAL, as it always has;
+//   * max_walkers: libcogdl_hip bounds n_walkers (ERANGE above (2^31 - 1) * 64, the bound the first walk kernel shipped
+//     with; its grid of n_walkers / 256 workgroups would fit gridDim.x for more); libcogdl_host has no such bound and
+//     passes INT64_MAX.
+inline int walk_args_status(const int64_t *indptr, const int64_t *indices, int64_t num_nodes, int64_t num_edges,
+                            const int64_t *start, int64_t n_walkers, int64_t length, const int64_t *walks, const int *flags,
+                            int64_t max_walkers) {
+    if (num_nodes < 0 || num_edges < 0 || n_walkers < 0 || length < 1 || !flags) return kArgsInvalid;
+    if (n_walkers > 0 && (!indptr || !start || !walks)) return kArgsInvalid;
+    if (num_edges > 0 && !indices) return kArgsInvalid;
+    if (length > 0x7fffffff || n_walkers > max_walkers) return kArgsRange;
+    return kArgsOk;
 }
 
 }  // namespace cogdl_walk

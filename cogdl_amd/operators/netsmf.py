@@ -23,7 +23,7 @@ and columns of nodes of degree 0 are empty in the sparsifier (the reference divi
 import torch
 
 from .. import _lib
-from .walk import _seed, raise_for_flags
+from .walk import _graph_checks, _seed, raise_for_flags
 
 __all__ = ["path_pairs", "path_counts", "sparsifier", "randomized_svd"]
 
@@ -35,14 +35,7 @@ _F32_EXACT = 2 ** 24     # float32 holds every integer up to here
 
 
 def _graph(name, indptr, indices, window):
-    if not (torch.is_tensor(indptr) and torch.is_tensor(indices)):
-        raise _lib.BackendError("%s: indptr / indices must be tensors" % name)
-    if indptr.dtype != torch.long or indices.dtype != torch.long:
-        raise _lib.BackendError("%s: indptr / indices must be int64 (got %s / %s)" % (name, indptr.dtype, indices.dtype))
-    if indptr.dim() != 1 or indices.dim() != 1 or indptr.numel() < 1:
-        raise _lib.BackendError("%s: indptr / indices must be 1-D (indptr non-empty)" % name)
-    if indices.device != indptr.device:
-        raise _lib.BackendError("%s: tensors on different devices: %s vs %s" % (name, indptr.device, indices.device))
+    _graph_checks(name, indptr, indices)
     if indptr.numel() - 1 > _I32_MAX:
         raise _lib.BackendError("%s: %d nodes; the pairs are int32 (limit 2^31 - 1)" % (name, indptr.numel() - 1))
     window = int(window)
@@ -59,15 +52,8 @@ def _pairs(indptr, indices, window, first, count, seed):
     if count == 0:
         return row, col
     flags = torch.empty(1, dtype=torch.int32, device=dev)
-    if dev.type == "cuda":
-        with _lib.on_device(dev):
-            rc = _lib.hip().cogdl_hip_netsmf_sample(_lib.ptr(indptr), _lib.ptr(indices), n, e, first, count, window, seed,
-                                                    _lib.ptr(row), _lib.ptr(col), _lib.ptr(flags), _lib.stream_of(indptr))
-        _lib.check(rc, "netsmf_sample")
-    else:
-        rc = _lib.host().cogdl_host_netsmf_sample(_lib.ptr(indptr), _lib.ptr(indices), n, e, first, count, window, seed,
-                                                  _lib.ptr(row), _lib.ptr(col), _lib.ptr(flags))
-        _lib.check_host(rc, "netsmf_sample")
+    _lib.twin_call("netsmf_sample", dev, _lib.ptr(indptr), _lib.ptr(indices), n, e, first, count, window, seed, _lib.ptr(row),
+                   _lib.ptr(col), _lib.ptr(flags))
     raise_for_flags("netsmf_sample", flags.item(), n)  # the one synchronisation
     return row, col
 

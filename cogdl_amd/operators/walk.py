@@ -39,7 +39,8 @@ _FLAG_TEXT = ((1, "a start id lies outside [0, %d)"), (2, "a neighbour id lies o
               (16, "a wanted type or a metapath id lies outside its range (%d nodes)"))
 
 
-def _graph_args(name, indptr, indices, start, length):
+def _graph_checks(name, indptr, indices):
+    """What every operator on an int64 CSR graph checks first (operators/netsmf.py too)."""
     if not (torch.is_tensor(indptr) and torch.is_tensor(indices)):
         raise _lib.BackendError("%s: indptr / indices must be tensors" % name)
     if indptr.dtype != torch.long or indices.dtype != torch.long:
@@ -48,6 +49,10 @@ def _graph_args(name, indptr, indices, start, length):
         raise _lib.BackendError("%s: indptr / indices must be 1-D (indptr non-empty)" % name)
     if indices.device != indptr.device:
         raise _lib.BackendError("%s: tensors on different devices: %s vs %s" % (name, indptr.device, indices.device))
+
+
+def _graph_args(name, indptr, indices, start, length):
+    _graph_checks(name, indptr, indices)
     if not torch.is_tensor(start):
         start = torch.as_tensor(start, dtype=torch.long, device=indptr.device)
     if start.dtype != torch.long:
@@ -99,40 +104,57 @@ def random_walk(indptr, indices, start, length, restart_p=0.0, seed=None, out=No
         flags = torch.empty(1, dtype=torch.int32, device=dev)
     elif not torch.is_tensor(flags) or flags.dtype != torch.int32 or flags.device != dev or flags.numel() != 1:
         raise _lib.BackendError("random_walk: flags must be a 1-element int32 tensor on %s" % dev)
-    if dev.type == "cuda":
-        with _lib.on_device(dev):
-            rc = _lib.hip().cogdl_hip_random_walk(_lib.ptr(indptr), _lib.ptr(indices), n, e, _lib.ptr(start), w, length,
-                                                  restart_p, seed, _lib.ptr(walks), _lib.ptr(flags), _lib.stream_of(indptr))
-        _lib.check(rc, "random_walk")
-    else:
-        rc = _lib.host().cogdl_host_random_walk(_lib.ptr(indptr), _lib.ptr(indices), n, e, _lib.ptr(start), w, length,
-                                                restart_p, seed, _lib.ptr(walks), _lib.ptr(flags))
-        _lib.check_host(rc, "random_walk")
+    _lib.twin_call("random_walk", dev, _lib.ptr(indptr), _lib.ptr(indices), n, e, _lib.ptr(start), w, length, restart_p, seed,
+                   _lib.ptr(walks), _lib.ptr(flags))
     if check:
         raise_for_flags("random_walk", flags.item(), n)  # the one synchronisation
     return walks
 
 
-# Rows sorted by column, once per structure: keyed on the two tensor OBJECTS (weak references) and vouched for by their
-# version counters, data pointers and sizes, like the identity memo of cogdl_amd/plan.py.  The value is the sorted indices
-# tensor, or None when the rows were sorted already.
-_SORTED = collections.OrderedDict()
-_SORTED_MAX = 8
+class _StructureMemo:
+    """Something derived from a graph's structure, once per structure: keyed on two or three tensor OBJECTS (weak references,
+    plus a hashable `extra`) and vouched for by their version counters, data pointers and sizes, like the identity memo of
+    cogdl_amd/plan.py.  The `limit` most recently used entries are kept.  A value holds None in place of the caller's own
+    tensors: the memo must not keep them alive."""
+
+    def __init__(self, limit=8):
+        self._entries, self._limit = collections.OrderedDict(), limit
+
+    def find(self, a, b, c=None, extra=None):
+        """-> (True, the value put for these tensor objects in their present state) or (False, the ticket to hand to put).
+        Runs in front of every launch, hence the unrolled compares."""
+        key = (id(a), id(b), id(c), extra)
+        state = (a._version, a.data_ptr(), a.numel(), b._version, b.data_ptr(), b.numel(),
+                 None if c is None else (c._version, c.data_ptr(), c.numel()))
+        hit = self._entries.get(key)
+        if hit is not None:
+            if hit[0] == state and hit[1]() is a and hit[2]() is b and (c is None or hit[3]() is c):
+                self._entries.move_to_end(key)
+                return True, hit[4]
+            del self._entries[key]
+        return False, (key, state, a, b, c)
+
+    def put(self, ticket, value):
+        key, state, a, b, c = ticket
+        try:
+            self._entries[key] = (state, weakref.ref(a), weakref.ref(b), None if c is None else weakref.ref(c), value)
+        except TypeError:
+            pass
+        while len(self._entries) > self._limit:
+            self._entries.popitem(last=False)
+
+    def clear(self):
+        self._entries.clear()
 
 
-def _state(indptr, indices):
-    return (indptr._version, indices._version, indptr.data_ptr(), indices.data_ptr(), indptr.numel(), indices.numel())
+_SORTED = _StructureMemo()  # (indptr, indices) -> the sorted indices tensor, or None when the rows were sorted already
 
 
 def sorted_rows(indptr, indices):
     """`indices` with every row sorted by column (the same tensor if it already is)."""
-    key = (id(indptr), id(indices))
-    hit = _SORTED.get(key)
-    if hit is not None:
-        if hit[0]() is indptr and hit[1]() is indices and hit[2] == _state(indptr, indices):
-            _SORTED.move_to_end(key)
-            return indices if hit[3] is None else hit[3]
-        del _SORTED[key]
+    found, memo = _SORTED.find(indptr, indices)
+    if found:
+        return indices if memo is None else memo
     n, e = indptr.numel() - 1, indices.numel()
     result = None
     if e > 1 and n > 0:
@@ -142,12 +164,7 @@ def sorted_rows(indptr, indices):
         if bool(((row[1:] == row[:-1]) & (indices[1:] < indices[:-1])).any()):
             by_col = torch.sort(indices, stable=True).indices
             result = indices[by_col[torch.sort(row[by_col], stable=True).indices]].contiguous()
-    try:
-        _SORTED[key] = (weakref.ref(indptr), weakref.ref(indices), _state(indptr, indices), result)
-    except TypeError:
-        pass
-    while len(_SORTED) > _SORTED_MAX:
-        _SORTED.popitem(last=False)
+    _SORTED.put(memo, result)
     return indices if result is None else result
 
 
@@ -167,28 +184,15 @@ def node2vec_walk(indptr, indices, start, length, p=1.0, q=1.0, seed=None, retur
     walks = torch.empty((w, length), dtype=torch.long, device=dev)
     fallback = torch.empty(w, dtype=torch.int32, device=dev) if return_fallback else None
     flags = torch.empty(1, dtype=torch.int32, device=dev)
-    if dev.type == "cuda":
-        with _lib.on_device(dev):
-            rc = _lib.hip().cogdl_hip_node2vec_walk(_lib.ptr(indptr), _lib.ptr(indices), n, e, _lib.ptr(start), w, length, p, q,
-                                                    trials, seed, _lib.ptr(walks), _lib.ptr(fallback), _lib.ptr(flags),
-                                                    _lib.stream_of(indptr))
-        _lib.check(rc, "node2vec_walk")
-    else:
-        rc = _lib.host().cogdl_host_node2vec_walk(_lib.ptr(indptr), _lib.ptr(indices), n, e, _lib.ptr(start), w, length, p, q,
-                                                  trials, seed, _lib.ptr(walks), _lib.ptr(fallback), _lib.ptr(flags))
-        _lib.check_host(rc, "node2vec_walk")
+    _lib.twin_call("node2vec_walk", dev, _lib.ptr(indptr), _lib.ptr(indices), n, e, _lib.ptr(start), w, length, p, q, trials,
+                   seed, _lib.ptr(walks), _lib.ptr(fallback), _lib.ptr(flags))
     raise_for_flags("node2vec_walk", flags.item(), n)
     return (walks, fallback) if return_fallback else walks
 
 
 # ---------------------------------------------------------------------------------------------------- metapath walk
 MAX_TYPES = 64
-_TYPED = collections.OrderedDict()  # (id(indptr), id(indices), id(node_type), T) -> weak refs, state, (seg, indices_t, int32 types)
-_TYPED_MAX = 8
-
-
-def _typed_state(indptr, indices, node_type):
-    return _state(indptr, indices) + (node_type._version, node_type.data_ptr(), node_type.numel())
+_TYPED = _StructureMemo()  # (indptr, indices, node_type), T -> (seg, indices_t, int32 types)
 
 
 def _typed_layout(indptr, indices, node_type, num_types=None):
@@ -215,16 +219,11 @@ def _typed_layout(indptr, indices, node_type, num_types=None):
         raise _lib.BackendError("%s: the number of node types must be in [1, %d] (got %d)" % (name, MAX_TYPES, t))
     if n * t > 2 ** 31 - 2:
         raise _lib.BackendError("%s: nodes x types = %d exceeds 2^31 - 2" % (name, n * t))
-    key = (id(indptr), id(indices), id(node_type), t)
-    hit = _TYPED.get(key)
-    if hit is not None:
-        if (hit[0]() is indptr and hit[1]() is indices and hit[2]() is node_type
-                and hit[3] == _typed_state(indptr, indices, node_type)):
-            _TYPED.move_to_end(key)
-            seg, indices_t, types32 = hit[4]  # (None: the caller's own tensor, which the cache must not keep alive)
-            return (indptr if seg is None else seg, indices if indices_t is None else indices_t,
-                    node_type if types32 is None else types32)
-        del _TYPED[key]
+    found, memo = _TYPED.find(indptr, indices, node_type, t)
+    if found:
+        seg, indices_t, types32 = memo  # (None: the caller's own tensor)
+        return (indptr if seg is None else seg, indices if indices_t is None else indices_t,
+                node_type if types32 is None else types32)
     if n and (int(node_type.min()) < 0 or int(node_type.max()) >= t):
         raise _lib.BackendError("%s: a node type lies outside [0, %d)" % (name, t))
     if int(indptr[0]) != 0 or int(indptr[-1]) != e or (n and bool((indptr[1:] < indptr[:-1]).any())):
@@ -240,14 +239,7 @@ def _typed_layout(indptr, indices, node_type, num_types=None):
         row = torch.repeat_interleave(torch.arange(n, device=indptr.device), indptr[1:] - indptr[:-1])
         seg, perm = coo2csr_index(row * t + node_type[indices].long(), None, n * t)  # stable: the order inside a type is kept
         value = (seg, indices[perm].contiguous(), types32)
-    try:
-        _TYPED[key] = (weakref.ref(indptr), weakref.ref(indices), weakref.ref(node_type),
-                       _typed_state(indptr, indices, node_type),
-                       (None if t == 1 else value[0], None if t == 1 else value[1], None if types32 is node_type else types32))
-    except TypeError:
-        pass
-    while len(_TYPED) > _TYPED_MAX:
-        _TYPED.popitem(last=False)
+    _TYPED.put(memo, (None if t == 1 else value[0], None if t == 1 else value[1], None if types32 is node_type else types32))
     return value
 
 
@@ -329,14 +321,8 @@ def metapath_walk(indptr, indices, node_type, start, schema, length, walker_path
     walks = torch.empty((w, length), dtype=torch.long, device=dev)
     lengths = torch.empty(w, dtype=torch.int32, device=dev) if return_lengths else None
     flags = torch.empty(1, dtype=torch.int32, device=dev)
-    args = (_lib.ptr(seg), _lib.ptr(indices_t), n, t, e, _lib.ptr(types32), _lib.ptr(start), _lib.ptr(walker_path), w, length,
-            _lib.ptr(pattern), _lib.ptr(path_off), len(paths), seed, _lib.ptr(walks), _lib.ptr(lengths), _lib.ptr(flags))
-    if dev.type == "cuda":
-        with _lib.on_device(dev):
-            rc = _lib.hip().cogdl_hip_metapath_walk(*args, _lib.stream_of(indptr))
-        _lib.check(rc, name)
-    else:
-        rc = _lib.host().cogdl_host_metapath_walk(*args)
-        _lib.check_host(rc, name)
+    _lib.twin_call(name, dev, _lib.ptr(seg), _lib.ptr(indices_t), n, t, e, _lib.ptr(types32), _lib.ptr(start),
+                   _lib.ptr(walker_path), w, length, _lib.ptr(pattern), _lib.ptr(path_off), len(paths), seed, _lib.ptr(walks),
+                   _lib.ptr(lengths), _lib.ptr(flags))
     raise_for_flags(name, flags.item(), n)
     return (walks, lengths) if return_lengths else walks

@@ -1,4 +1,4 @@
-"""metapath_walk_kernel (csrc/walk.hip) on the GPU: bit-for-bit equal to the host twin, `lengths` included, over the case
+"""The metapath walk (walk_kernel<MetapathRule>, csrc/walk.hip) on the GPU: bit-for-bit equal to the host twin, `lengths` included, over the case
 graphs, the length and walker sweeps and several metapaths; stream use; the T == 1 identity with random_walk; an R-MAT run
 under the brute-force checker; error flags equal to the host's instead of faults."""
 import numpy as np

@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "metapath_corridor.npz")
 QUANTILE = 1.0 - 1e-6
 LENGTHS = [1, 2, 7, 8, 9, 16, 17]
-WALKERS = [0, 1, 63, 64, 65, 256, 257]
+WALKERS = [0, 1, 63, 64, 65, 255, 256, 257]
 
 
 def schemas_for(node_type):

@@ -51,25 +51,46 @@ def test_gpu_equals_host_on_every_graph(name, monkeypatch):
     assert torch.equal(host, gpu), "node2vec with the exact fallback forced"
 
 
-@pytest.mark.parametrize("w", [0, 1, 63, 64, 65, 100003])
-def test_gpu_equals_host_over_walker_counts(w):
+@pytest.fixture(scope="module")
+def rmat():
     indptr, indices, n = rmat_graph()
+    return (indptr, indices), (indptr.to(DEV), indices.to(DEV)), n
+
+
+def n2v_both(rmat, start, length, **kw):
+    """node2vec_walk with its fallback counts on both sides -> the walks; asserts that walks and counts are equal."""
+    host_g, gpu_g, _ = rmat
+    hw, hf = node2vec_walk(*host_g, start, length, return_fallback=True, **kw)
+    gw, gf = node2vec_walk(*gpu_g, start.to(DEV), length, return_fallback=True, **kw)
+    assert gw.is_cuda and gw.dtype == torch.int64 and tuple(gw.shape) == (start.numel(), length)
+    assert gf.is_cuda and gf.dtype == torch.int32 and tuple(gf.shape) == (start.numel(),)
+    assert torch.equal(hw, gw.cpu()) and torch.equal(hf, gf.cpu())
+    return hw
+
+
+# 255 / 256 / 257: a workgroup short by a lane, exactly one, one lane into a second (parked lanes, the last workgroup)
+@pytest.mark.parametrize("w", [0, 1, 63, 64, 65, 255, 256, 257, 100003])
+def test_gpu_equals_host_over_walker_counts(rmat, w):
+    host_g, gpu_g, n = rmat
     start = torch.randint(0, n, (w,), generator=torch.Generator().manual_seed(w))
-    host, gpu = both(random_walk, indptr, indices, start, 17, restart_p=0.3, seed=70)
-    assert tuple(gpu.shape) == (w, 17) and torch.equal(host, gpu)
-    host, gpu = both(node2vec_walk, indptr, indices, start, 17, p=0.25, q=4.0, seed=71)
-    assert tuple(gpu.shape) == (w, 17) and torch.equal(host, gpu)
+    host = random_walk(*host_g, start, 17, restart_p=0.3, seed=70)
+    gpu = random_walk(*gpu_g, start.to(DEV), 17, restart_p=0.3, seed=70)
+    assert gpu.is_cuda and gpu.dtype == torch.int64 and tuple(gpu.shape) == (w, 17) and torch.equal(host, gpu.cpu())
+    n2v_both(rmat, start, 17, p=0.25, q=4.0, seed=71)
 
 
-@pytest.mark.parametrize("length", [1, 2, 80, 257])
-def test_gpu_equals_host_over_lengths(length):
-    indptr, indices, n = rmat_graph()
+# 7 / 8 / 9 / 16: one short of a tile of the kernel's staging, exactly one tile, one past it, two tiles
+@pytest.mark.parametrize("length", [1, 2, 7, 8, 9, 16, 80, 257])
+def test_gpu_equals_host_over_lengths(rmat, length, monkeypatch):
+    host_g, gpu_g, n = rmat
     start = torch.randint(0, n, (1000,), generator=torch.Generator().manual_seed(length))
     for restart in (0.0, 0.3):
-        host, gpu = both(random_walk, indptr, indices, start, length, restart_p=restart, seed=80)
-        assert tuple(gpu.shape) == (1000, length) and torch.equal(host, gpu)
-    host, gpu = both(node2vec_walk, indptr, indices, start, length, p=4.0, q=0.25, seed=81)
-    assert torch.equal(host, gpu)
+        host = random_walk(*host_g, start, length, restart_p=restart, seed=80)
+        gpu = random_walk(*gpu_g, start.to(DEV), length, restart_p=restart, seed=80)
+        assert gpu.is_cuda and gpu.dtype == torch.int64 and tuple(gpu.shape) == (1000, length) and torch.equal(host, gpu.cpu())
+    n2v_both(rmat, start, length, p=4.0, q=0.25, seed=81)
+    monkeypatch.setattr(walk_mod, "NODE2VEC_TRIALS", 2)  # (so that the counts are not all zero)
+    n2v_both(rmat, start, length, p=0.25, q=4.0, seed=82)
 
 
 def test_fallback_counts_equal_the_host(monkeypatch):

@@ -16,6 +16,7 @@ import scipy.sparse as sp
 import torch
 from scipy.stats import chi2
 
+from _walk_cases import GRAPHS, csr_of, n2v_graph, path_with_sink, random_with_isolated
 from cogdl_amd import _lib
 from cogdl_amd.operators import node2vec_walk, random_walk
 from cogdl_amd.operators import walk as walk_mod
@@ -25,42 +26,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STAGED = os.path.join(ROOT, "oracle", "_ref", "pkg")
 REF = STAGED if os.path.isdir(os.path.join(STAGED, "cogdl")) else os.environ.get("COGDL_REFERENCE", "")
 QUANTILE = 1.0 - 1e-6
-
-
-def csr_of(row, col, n):
-    """Stable CSR (rows keep their COO order, duplicates kept) as int64 tensors."""
-    row, col = np.asarray(row, dtype=np.int64), np.asarray(col, dtype=np.int64)
-    order = np.argsort(row, kind="stable")
-    indptr = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(np.bincount(row, minlength=n), out=indptr[1:])
-    return torch.from_numpy(indptr), torch.from_numpy(col[order].copy())
-
-
-def path_with_sink():
-    n = 6
-    return csr_of(np.arange(n - 1), np.arange(1, n), n) + (n,)
-
-
-def star():
-    leaves = np.arange(1, 5001)
-    zeros = np.zeros(5000, dtype=np.int64)
-    return csr_of(np.concatenate([zeros, leaves]), np.concatenate([leaves, zeros]), 5001) + (5001,)
-
-
-def random_with_isolated():
-    rng = np.random.default_rng(5)
-    n = 400
-    row, col = rng.integers(0, 300, 3000), rng.integers(0, n, 3000)  # nodes 300.. have no out-edges
-    return csr_of(row, col, n) + (n,)
-
-
-def duplicates():
-    row = [0, 0, 0, 1, 1, 2, 2, 2, 2, 3]
-    col = [1, 1, 2, 0, 0, 3, 3, 3, 0, 2]
-    return csr_of(row, col, 4) + (4,)
-
-
-GRAPHS = {"path": path_with_sink, "star": star, "random": random_with_isolated, "dup": duplicates}
 
 
 def check_transitions(indptr, indices, n, start, walks, restart):
@@ -238,14 +203,6 @@ def test_two_steps_with_restart_follow_the_exact_law(node):
     start = torch.full((1_000_000,), node, dtype=torch.long)
     walks = random_walk(indptr, indices, start, 3, restart_p=restart, seed=2000 + node)
     assert_chi_square(np.bincount(walks[:, 2].numpy(), minlength=n), law, "two steps from node %d, restart 0.3" % node)
-
-
-def n2v_graph():
-    """Symmetric.  At (t, v) = (0, 1) the neighbours of v are 0 (= t), 2 (adjacent to t), 3 and 4 (not adjacent to t)."""
-    pairs = [(0, 1), (1, 2), (0, 2), (1, 3), (1, 4), (3, 4)]
-    row = [a for a, b in pairs] + [b for a, b in pairs]
-    col = [b for a, b in pairs] + [a for a, b in pairs]
-    return csr_of(row, col, 5) + (5,)
 
 
 def third_node_counts(walks, n):
