@@ -12,7 +12,11 @@ include/cogdl_hip.h for f16 / bf16 csr_spmm, mhspmm and the fused GAT operator).
 
 `want` is the float64 result on the ROUNDED inputs.  A store that truncates, or a value rounded twice, is outside this bound
 for a large share of the outputs (tests/test_halfprec_bound_cpu.py pins that), while the old 2^-7 / 2^-10 relative bounds --
-four units roundoff -- cannot see either."""
+four units roundoff -- cannot see either.
+
+Two more tools for the same promise:  assert_exact  -- with integer data every fp32 partial sum is exact, the slack is zero and
+the result has to be the float64 result cast once, ties to even --  and  row_softmax / softmax_terms  -- the float64 reference
+of csr_edge_softmax and the `terms` its bound takes (derived in tests/test_halfprec_softmax_gpu.py)."""
 import numpy as np
 import torch
 
@@ -70,3 +74,71 @@ def assert_close(got, want, scale, terms, dtype, what):
     if torch.is_tensor(got):
         got = got.detach().float().cpu().numpy()
     assert_within(got, want, bound(want, scale, terms, dtype), what)
+
+
+def assert_exact(got, want64, scale, dtype, what):
+    """Exact arithmetic: the inputs are small integers (or multiples of a power of two), so every product and every fp32 partial
+    sum -- in ANY order -- is exact as long as the sum of the absolute terms `scale` stays below 2^24 (asserted here).  The only
+    rounding left is the store's, there is no slack, and ties occur (257 in bf16 is one): `got` (a tensor of `dtype`) has to
+    be the float64 result cast ONCE by torch (round to nearest, ties to even; beyond the range: inf), bit for bit -- only the sign
+    of a zero is left open (a sum of exact terms that cancel is +0 or -0 by the order they were added in)."""
+    scale = np.asarray(scale, dtype=np.float64)
+    assert scale.shape == np.shape(want64) and bool((scale < 2.0 ** 24).all()), "%s: the sums are not exact in fp32" % what
+    want = torch.from_numpy(np.ascontiguousarray(want64, dtype=np.float64)).to(dtype)
+    got = got.detach().cpu()
+    assert got.dtype == dtype and got.shape == want.shape, "%s: %s %s, expected %s %s" % (what, got.dtype, tuple(got.shape), dtype,
+                                                                                          tuple(want.shape))
+    gb, wb = got.contiguous().view(torch.int16), want.contiguous().view(torch.int16)
+    bad = (gb != wb) & ~((got == 0) & (want == 0))
+    if bool(bad.any()):
+        i = int(torch.nonzero(bad.flatten())[0])
+        raise AssertionError("%s: %d of %d elements are not the exact sum rounded once; first at flat index %d: got %r, exact %r "
+                             "-> %r" % (what, int(bad.sum()), bad.numel(), i, float(got.flatten()[i]),
+                                        float(np.asarray(want64).flat[i]), float(want.flatten()[i])))
+
+
+def row_softmax(rowptr, v, g=None, s=None):
+    """Float64 softmax over the rows of a CSR structure, per head: rowptr [m + 1], v [E, H] (empty rows are fine).
+    -> (want [E, H], A [m, H]) with A = max over the row of |v - max_row| (0 for an empty row); with an upstream gradient g [E, H]
+    also the backward  want_g = s * (g - sum_row s * g)  and the sum of its absolute terms  scale_g = s * (|g| + sum_row |s * g|),
+    both [E, H], for s = `s` if given (the forward output a kernel SAVED, so that the two passes are judged separately), else
+    `want`.  v = None (with g and s): the backward alone -> (None, None, want_g, scale_g)."""
+    rowptr = np.asarray(rowptr, dtype=np.int64)
+    m = rowptr.shape[0] - 1
+    row = np.repeat(np.arange(m), np.diff(rowptr))
+    if v is None:  # the backward alone, from a saved output
+        g, s = np.asarray(g, dtype=np.float64), np.asarray(s, dtype=np.float64)
+        dot, dot_abs = np.zeros((m, s.shape[1])), np.zeros((m, s.shape[1]))
+        np.add.at(dot, row, s * g)
+        np.add.at(dot_abs, row, np.abs(s * g))
+        return None, None, s * (g - dot[row]), np.abs(s) * (np.abs(g) + dot_abs[row])
+    v = np.asarray(v, dtype=np.float64)
+    h = v.shape[1]
+    mx = np.full((m, h), -np.inf)
+    np.maximum.at(mx, row, v)
+    d = v - mx[row]
+    e = np.exp(d)
+    tot = np.zeros((m, h))
+    np.add.at(tot, row, e)
+    want = e / tot[row]
+    spread = np.zeros((m, h))
+    np.maximum.at(spread, row, np.abs(d))
+    if g is None:
+        return want, spread
+    g = np.asarray(g, dtype=np.float64)
+    s = want if s is None else np.asarray(s, dtype=np.float64)
+    dot, dot_abs = np.zeros((m, h)), np.zeros((m, h))
+    np.add.at(dot, row, s * g)
+    np.add.at(dot_abs, row, np.abs(s * g))
+    return want, spread, s * (g - dot[row]), np.abs(s) * (np.abs(g) + dot_abs[row])
+
+
+SOFTMAX_MARGIN = 16  # terms beyond the row's additions: the division, the difference v - max, the merge of piece records
+
+
+def softmax_terms(rowptr, spread):
+    """`terms` of bound() for every element of a row softmax (tests/test_halfprec_softmax_gpu.py derives them):
+    forward  deg + ceil(A) + 16 per (row, head) -> [E, H];  backward  deg + 16 -> [E, 1]."""
+    deg = np.diff(np.asarray(rowptr, dtype=np.int64))
+    row = np.repeat(np.arange(deg.shape[0]), deg)
+    return (deg[:, None] + np.ceil(spread) + SOFTMAX_MARGIN)[row], (deg + SOFTMAX_MARGIN)[row][:, None]

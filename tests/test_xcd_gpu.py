@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from _xcd_graphs import KINDS, graph as _graph
 from cogdl_amd import synth, xcdplan
 from cogdl_amd.operators.fused_gat import fused_gat_dropout_func, edge_dropout_mask
 from cogdl_amd.operators.spmm import SPMMFunction, csr_spmm_raw, csr_spmm_xcd_raw
@@ -28,24 +29,6 @@ def forced(monkeypatch):
     xcdplan.XPLANS.clear()
     yield
     xcdplan.XPLANS.clear()
-
-
-def _graph(kind):
-    if kind == "hubs":  # hubs longer than several pieces, medium rows around SPLIT, empty rows
-        g = synth.hub_csr(300, 257, base_deg=6, hubs=((3, 129), (4, 1000), (17, 5000), (18, 257), (40, 65), (41, 64), (100, 20000), (299, 700)),
-                           seed=5)  # (row 100: ~80 parts -- merged by a whole workgroup)
-    elif kind == "one_owner":  # every long row's edges name ONE column: a single owner XCD, seven absent parts
-        g = synth.hub_csr(70, 50, base_deg=2, hubs=((0, 300), (5, 66), (69, 513)), seed=2)
-        g.colind[g.rowptr[0]:g.rowptr[1]] = 7
-        g.colind[g.rowptr[69]:g.rowptr[70]] = 49
-    elif kind == "short":  # no long row at all: every slot whole, no records
-        g = synth.random_csr(1000, 333, 8, seed=3)
-    else:  # rectangular, more rows than columns, R-MAT-like skew
-        g = synth.hub_csr(2000, 97, base_deg=30, hubs=((1, 4000), (2, 4001), (1999, 2047)), seed=7)
-    return g
-
-
-KINDS = ["hubs", "one_owner", "short", "rect"]
 
 
 def _close(got, want, scale, tol, what, atol=1e-30):
