@@ -118,6 +118,11 @@ class _SpGEMM(torch.autograd.Function):
         rA, cA, vA, rB, cB, vB, rC, cC = ctx.saved_tensors
         m, k, _ = ctx.dims
         lib = _lib.hip()
+        if cC.numel() == 0:
+            # C has no entry (an empty operand, or A's columns meet only empty rows of B): both gradients are zero, and
+            # the empty colC / g (and an empty operand's arrays) have no address for the entry points, which refuse NULL
+            return (torch.zeros_like(vA) if ctx.needs_input_grad[0] else None,
+                    torch.zeros_like(vB) if ctx.needs_input_grad[1] else None, None, None, None, None, None, None, None)
         g = g.contiguous()
         stream = _lib.stream_of(g)
         gA = gB = None
@@ -151,7 +156,8 @@ def spgemm(rowptrA, colA, valA, rowptrB, colB, valB, n):
     """C = A . B with A [m, k] and B [k, n] in int32 CSR (m = rowptrA.numel() - 1, k = rowptrB.numel() - 1; column ids
     of A below k, of B below n) -> (rowptrC int32 [m+1], colC int32, valC float32): canonical CSR (columns ascending and
     unique per row) with the STRUCTURAL pattern -- an entry whose products cancel is kept as 0.0, as torch.sparse.mm
-    keeps it.  A and B need not be canonical.  Differentiable in valA and valB.  Bit-identical results on every call.
+    keeps it.  A and B need not be canonical.  Differentiable in valA and valB (a product without any entry gives zero
+    gradients of the operands' shapes).  Bit-identical results on every call.
     Limits (BackendError with COGDL_HIP_ERANGE): m, k, n and nnz(C) below 2^31, and the rows with more than 4096 products
     (the global-memory path) at most COGDL_HIP_SEGMENT_MAX_EDGES = 2^31 - 2^20 products in all.
     Both CSRs are validated first (rowptr starts at 0, never decreases, ends at nnz; column ids in range): one more
