@@ -171,6 +171,9 @@ HIP_SIGNATURES = {
     "cogdl_hip_sort_pool_workspace_bytes": ([_i64], _sz),
     "cogdl_hip_sort_pool_fwd": ([_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _sz, _vp], _i32),
     "cogdl_hip_sort_pool_bwd": ([_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp], _i32),
+    # polynomial filter step (csrc/polyfilter.hip)
+    "cogdl_hip_csr_filter_step": ([_vp] * 5 + [_i64, _i64, _i64, _i32, _f32, _f32, _vp, _f32, _vp, _f32, _vp, _vp, _f32, _vp, _sz, _vp],
+                                  _i32),
 }
 
 MAX_SEGMENTS = 64  # COGDL_HIP_MAX_SEGMENTS
@@ -205,6 +208,7 @@ HOST_SIGNATURES = {
     "cogdl_host_segment_pool_bwd": ([_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp], _i32),
     "cogdl_host_sort_pool_fwd": ([_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp], _i32),
     "cogdl_host_sort_pool_bwd": ([_vp, _vp, _i64, _i64, _i64, _i64, _vp], _i32),
+    "cogdl_host_csr_filter_step": ([_vp] * 5 + [_i64, _i64, _i64, _i32, _f32, _f32, _vp, _f32, _vp, _f32, _vp, _vp, _f32], _i32),
 }
 
 EUNSUPPORTED = 7  # COGDL_HIP_EUNSUPPORTED

@@ -489,3 +489,66 @@ int cogdl_host_metapath_walk(const int64_t *seg, const int64_t *indices_t, int64
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- polynomial filter step (the twin of csrc/polyfilter.hip)
+// The statement order of include/cogdl_hip.h (cogdl_hip_csr_filter_step), one row at a time: a sequential fp32 sum in CSR
+// order, then the epilogue with every product and sum rounded separately (-ffp-contract=off).  Columns go in blocks whose
+// sums sit on the stack, and a column's operands are all read before its out / acc are written: out may be z1 or z2.
+namespace {
+bool ranges_overlap(const void *p, const void *q, size_t bytes) {
+    if (!p || !q) return false;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return a < b + bytes && b < a + bytes;
+}
+}  // namespace
+
+extern "C" int cogdl_host_csr_filter_step(const int32_t *rowptr, const int32_t *colind, const float *val, const float *x, float *out,
+                                          int64_t n, int64_t k, int64_t nnz, int dtype, float a, float b, const float *z1, float c1,
+                                          const float *z2, float c2, const float *dst_scale, float *acc, float d) {
+    if (n < 0 || k < 0 || nnz < 0 || dtype != 0) return COGDL_HOST_EINVAL;
+    if (n == 0 || k == 0) return COGDL_HOST_OK;
+    if (!rowptr || !x || !out || (nnz > 0 && !colind)) return COGDL_HOST_EINVAL;
+    const size_t bytes = (size_t)n * (size_t)k * sizeof(float);
+    if (ranges_overlap(out, x, bytes) || ranges_overlap(acc, x, bytes) || ranges_overlap(out, acc, bytes)) return COGDL_HOST_EINVAL;
+    if ((z1 != out && ranges_overlap(out, z1, bytes)) || (z2 != out && ranges_overlap(out, z2, bytes))) return COGDL_HOST_EINVAL;
+    if ((z1 != acc && ranges_overlap(acc, z1, bytes)) || (z2 != acc && ranges_overlap(acc, z2, bytes))) return COGDL_HOST_EINVAL;
+    if (rowptr[0] != 0 || rowptr[n] != nnz) return COGDL_HOST_EINVAL;
+    int bad = 0;
+#pragma omp parallel for schedule(dynamic, 64) reduction(| : bad) if ((nnz + n) * k >= (1 << 16))
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t e0 = rowptr[i], e1 = rowptr[i + 1];
+        if (e0 < 0 || e1 < e0 || e1 > nnz) {
+            bad |= 1;
+            continue;
+        }
+        for (int64_t j0 = 0; j0 < k; j0 += kColBlock) {
+            const int w = (int)std::min<int64_t>(kColBlock, k - j0);
+            float t[kColBlock];
+            for (int j = 0; j < w; ++j) t[j] = 0.f;
+            for (int64_t e = e0; e < e1; ++e) {
+                const int64_t c = colind[e];
+                if (c < 0 || c >= n) {
+                    bad |= 1;
+                    continue;
+                }
+                const float *xr = x + c * k + j0;
+                if (val) {
+                    const float v = val[e];
+                    for (int j = 0; j < w; ++j) t[j] = t[j] + v * xr[j];
+                } else {
+                    for (int j = 0; j < w; ++j) t[j] = t[j] + xr[j];
+                }
+            }
+            const int64_t off = i * k + j0;
+            for (int j = 0; j < w; ++j) {
+                float y = a * (dst_scale ? dst_scale[i] * t[j] : t[j]);
+                if (b != 0.f) y = y + b * x[off + j];
+                if (z1) y = y + c1 * z1[off + j];
+                if (z2) y = y + c2 * z2[off + j];
+                out[off + j] = y;
+                if (acc) acc[off + j] = acc[off + j] + d * y;
+            }
+        }
+    }
+    return bad ? COGDL_HOST_ERANGE : COGDL_HOST_OK;
+}

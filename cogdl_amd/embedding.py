@@ -6,6 +6,7 @@ library's skip-gram operator -- what the reference's DeepWalk / Node2vec do thro
     node2vec(graph_or_csr, dim, walk_length, walk_num, window, epochs, p, q) -> float32 [N, dim]
     netsmf(graph_or_csr, dim, window, negative, rounds)                     -> float32 [N, dim]
     metapath2vec(graph_or_csr, node_type, schema, dim, walk_length, walk_num, window, epochs) -> float32 [N, dim]
+    prone(graph_or_csr, dim, step, mu, theta)                               -> float32 [N, dim]
 
 `graph_or_csr` is a cogdl Graph (its row_indptr / col_indices are used on the device they live on) or an
 (indptr, indices) pair of int64 tensors.  Each of the walk_num passes starts one walk at every node, in an order shuffled
@@ -16,6 +17,10 @@ cogdl/models/emb/metapath2vec.py:87-125) ends a walk where no neighbour has the 
 
 netsmf is the matrix-factorisation member of the family (cogdl/models/emb/netsmf.py): path samples counted into a sparse
 matrix, the sparsifier's log transform, a randomized SVD -- all three from cogdl_amd/operators/netsmf.py, nothing trained.
+
+prone is the other one (cogdl/models/emb/prone.py): an elementwise transform of the adjacency's entries, the same randomized
+SVD, the spectral propagation of cogdl_amd/operators/spectral.py (one fused filter step per sparse product) and a dense
+embedding from the [dim, dim] Gram matrix.
 """
 import math
 
@@ -132,3 +137,74 @@ def netsmf(graph_or_csr, dim=128, window=10, negative=1, rounds=100, seed=None):
     emb = u * s.sqrt()
     norm = emb.norm(dim=1, keepdim=True)
     return torch.where(norm > 0, emb / norm.clamp_min(1e-30), torch.zeros_like(emb))
+
+
+def prone_prefactorization(indptr, indices):
+    """The matrix ProNE factorises (prone.py:74-92) for a simple graph with unit weights -> CSR (rowptr int32, col int32, val
+    float32) with the graph's own pattern, on its device: C1 = the l1 row-normalised adjacency, neg_j = colsum_j(C1)^0.75 /
+    sum_k colsum_k(C1)^0.75, entry (i, j) = log(C1_ij) - log(neg_j), with the reference's `<= 0 -> 1` replacement in front
+    of each log.  The column sums are float32 sums in increasing row order: the library's transpose (csr2csc; a stable sort
+    on the CPU) and its segment sum, no float atomics; the rest is elementwise float64 on the device, rounded to float32
+    once.  Rows and columns of nodes of degree 0 are empty."""
+    from .operators.netsmf import _transpose
+    from .operators.readout import segment_pool
+
+    n = indptr.numel() - 1
+    rowptr, col = indptr.int().contiguous(), indices.int().contiguous()
+    deg = (indptr[1:] - indptr[:-1])
+    rows = torch.repeat_interleave(torch.arange(n, device=indptr.device), deg)
+    c1 = (1.0 / deg.float())[rows].contiguous()  # (a row with an entry has deg >= 1)
+    colptr, _, c1_t = _transpose(rowptr, col, c1, n)
+    colsum = segment_pool(c1_t.reshape(-1, 1).contiguous(), colptr.int().contiguous(), "sum").reshape(-1).double()
+    neg = colsum.pow(0.75)
+    neg = neg / neg.sum()
+    c1d, negd = c1.double(), neg[indices]
+    c1d = torch.where(c1d <= 0, torch.ones_like(c1d), c1d)
+    negd = torch.where(negd <= 0, torch.ones_like(negd), negd)
+    return rowptr, col, (c1d.log() - negd.log()).float().contiguous()
+
+
+def dense_embedding(x):
+    """get_embedding_dense (cogdl/utils/prone_utils.py:232-241) of a tall [N, dim] matrix without a device solver: the
+    [dim, dim] Gram matrix X^T X in float64 on x's device, its eigen-decomposition V diag(lam) V^T on the host in float64,
+    then U sqrt(S) = X V S^(-1/2) with S = sqrt(lam) (descending) and l2-normalised rows -> float32 [N, dim].  Directions
+    whose eigenvalue is below 1e-12 of the largest come out as zero columns; a zero row stays zero.  Columns are determined
+    up to sign, as singular vectors are."""
+    xd = x.double()
+    gram = (xd.t() @ xd).cpu()
+    lam, v = torch.linalg.eigh((gram + gram.t()) / 2)
+    lam, v = lam.flip(0), v.flip(1)
+    top = float(lam[0]) if lam.numel() else 0.0
+    good = lam > 1e-12 * top if top > 0.0 else torch.zeros_like(lam, dtype=torch.bool)
+    w = torch.zeros_like(v)
+    w[:, good] = v[:, good] * lam[good].pow(-0.25)
+    emb = xd @ w.to(x.device)
+    norm = emb.norm(dim=1, keepdim=True)  # (float64 up to here: the result is rounded to float32 once)
+    return torch.where(norm > 0, emb / norm.clamp_min(1e-300), torch.zeros_like(emb)).float()
+
+
+def prone(graph_or_csr, dim=128, step=5, mu=0.2, theta=0.5, seed=None):
+    """ProNE on a simple symmetric graph with unit weights, without self loops -> float32 [N, dim] on the graph's device:
+    the pre-factorisation matrix, U sqrt(S) of its randomized SVD (n_iter = 5) with l2-normalised rows, the spectral
+    propagation spectral_filter("prone", order=step, mu=mu, s=theta) -- ProNE.forward hands (step, mu, theta) to
+    _chebyshev_gaussian's positional (order, mu, s), whose defaults carry the two names' values the other way round; what it
+    does is followed, not the defaults -- and the dense embedding of the result.  step == 1 returns the factorisation's
+    embedding as it is, as the reference does."""
+    from .operators.netsmf import randomized_svd
+    from .operators.spectral import spectral_filter
+
+    dim, step = int(dim), int(step)
+    if step < 1:
+        raise ValueError("step must be >= 1 (got %d)" % step)
+    indptr, indices = _csr(graph_or_csr)
+    n = indptr.numel() - 1
+    if not 1 <= dim <= n:
+        raise ValueError("dim must be in [1, N = %d] (got %d)" % (n, dim))
+    rowptr, col, val = prone_prefactorization(indptr, indices)
+    u, s = randomized_svd(rowptr, col, val, n, dim, n_iter=5, seed=_seed(seed))
+    feat = u * s.sqrt()
+    norm = feat.norm(dim=1, keepdim=True)
+    feat = torch.where(norm > 0, feat / norm.clamp_min(1e-30), torch.zeros_like(feat)).contiguous()
+    if step == 1:
+        return feat
+    return dense_embedding(spectral_filter("prone", rowptr, col, feat, order=step, mu=mu, s=theta))

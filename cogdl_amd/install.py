@@ -40,7 +40,7 @@ _finder = None
 
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
             metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False, readout=False,
-            relational=False, genconv=False, disengcn=False, contrast=False, netsmf=False, metapath=False):
+            relational=False, genconv=False, disengcn=False, contrast=False, netsmf=False, metapath=False, prone=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -134,6 +134,18 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     imports gensim, so where gensim is absent cogdl_amd.gensim_compat is registered first, as skipgram=True does.  A schema
     item that is not an integer, a metapath whose first item differs from its last and a data.pos that is not an integer
     tensor reach the reference's forward.
+    prone=True rebinds ProNE.forward in cogdl.models.emb.prone, and `propagate` in cogdl.utils.prone_utils with its by-name copy
+    in cogdl.models.emb.pronepp (opt-in: float32 where the reference runs scipy in float64, the library's randomized SVD where
+    it runs sklearn's, a zero row of the factorisation for a node without edges) to cogdl_amd.prone_compat: the simple
+    symmetric structure of edge_index is built on the graph's device and cogdl_amd.embedding.prone runs there -- the
+    pre-factorisation matrix, the randomized SVD, the spectral propagation as one fused filter step per sparse product
+    (cogdl_amd/operators/spectral.py: HIP kernel for a graph on the GPU, the OpenMP host twin otherwise) and the dense embedding
+    -- with the same return value (features_matrix as numpy [N, dim], or the dict with return_dict=True).  `propagate` keeps
+    its signature and runs the heat / ppr / gaussian / prone filters on the GPU when one is visible (the host twin otherwise),
+    returning float64 numpy: ProNE++'s search and the `--enhance prone` / `prone++` post-processing inherit it.  A graph whose
+    edge weights are not all equal, a graph with self loops, a graph without edges and step == 1 reach the reference's
+    forward; the "sc" filter, any other name and a matrix that is not square with unit entries and an empty diagonal reach the
+    reference's propagate.
     linear=True additionally routes torch.nn.functional.linear -- i.e. the unchanged nn.Linear inside every CogDL
     layer -- through cogdl_amd.linear (hand-written MFMA weight gradient for full-graph shapes)."""
     global _finder
@@ -232,6 +244,17 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
         _import_target(metapath_compat._MODULE, "metapath")
         if not metapath_compat.install():
             raise _lib_error("install(metapath=True): Metapath2vec.forward could not be rebound")
+    if prone:
+        from . import prone_compat
+
+        _import_target(prone_compat._MODULE, "prone")
+        _import_target(prone_compat._UTILS, "prone")
+        try:  # (the module that copied `propagate` by name; it needs optuna, and is rebound where it imports)
+            importlib.import_module(prone_compat._HOLDER)
+        except ImportError:
+            pass
+        if not prone_compat.install():
+            raise _lib_error("install(prone=True): ProNE.forward / propagate could not be rebound")
     su = sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):

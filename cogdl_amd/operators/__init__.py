@@ -25,6 +25,9 @@
 
     netsmf.py        path_pairs, path_counts, sparsifier, randomized_svd (also exported here)   (models/emb/netsmf.py)
 
+    spectral.py      filter_step, bessel_i, spectral_filter (also exported here)   (cogdl/utils/prone_utils.py:26-176,
+                                                                                    ProNE._chebyshev_gaussian, models/emb/prone.py)
+
     ops.py           scatter_add, op_aggr, s_*_e_sum / s_*_e_mean (fused HIP), s_*_e, s_*_t   (cogdl/operators/ops.py)
 
 Submodules are imported lazily: GPU modules load libcogdl_hip.so at import and raise if it
@@ -69,4 +72,8 @@ def __getattr__(name):
         from . import netsmf
 
         return getattr(netsmf, name)
+    if name in ("filter_step", "bessel_i", "spectral_filter"):
+        from . import spectral
+
+        return getattr(spectral, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

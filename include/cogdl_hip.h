@@ -1104,6 +1104,37 @@ COGDL_API int cogdl_hip_sort_pool_fwd(const float *x, const int32_t *ptr, int64_
 COGDL_API int cogdl_hip_sort_pool_bwd(const float *grad, const int32_t *idx, int64_t N, int64_t B, int64_t F, int64_t k,
                             float *grad_x, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * One step of a polynomial graph filter (added within ABI v9: a new symbol only; csrc/polyfilter.hip).  What the spectral
+ * propagation of ProNE and the heat-kernel / PPR / Gaussian filters iterate (cogdl/utils/prone_utils.py:26-176: a
+ * three-term recurrence on an [n, k] matrix, there one scipy product plus 2-5 elementwise passes per term), as ONE launch.
+ * For a square CSR structure (int32 rowptr [n + 1], colind [nnz], val fp32 [nnz] or NULL: unweighted), fp32 row-major
+ * [n, k] tensors and host scalars:
+ *     t[i,:]   = sum over the row's edges of val[e] * x[colind[e],:]
+ *     s        = dst_scale[i] * t[i,:]                 (only when dst_scale is given)
+ *     y        = a * s
+ *     y        = y + b  * x[i,:]                       (only when b != 0)
+ *     y        = y + c1 * z1[i,:]                      (only when z1 is given)
+ *     y        = y + c2 * z2[i,:]                      (only when z2 is given)
+ *     out[i,:] = y
+ *     acc[i,:] = acc[i,:] + d * y                      (only when acc is given)
+ * Arithmetic: t is cogdl_hip_csr_spmm's sum for the same operands, bit for bit, long rows included (the same functor with
+ * the launch geometry csr_spmm takes at this k and these x / out).  Every product and every sum of the epilogue is a
+ * separately rounded fp32 operation, left to right as written (no fused multiply-add).  An absent operand is never read and
+ * its term is skipped, not multiplied by zero.  A row without edges has t = 0 and still gets its epilogue.
+ * Aliasing: out may be z1 or z2, acc may be z1 or z2 (each lane reads its columns before it writes them).  out overlapping
+ * x or acc, acc overlapping x, or a z that overlaps out / acc without being it: COGDL_HIP_EINVAL.
+ * dtype != COGDL_HIP_F32: COGDL_HIP_EUNSUPPORTED.  n == 0 or k == 0: success, nothing launched.  k or nnz beyond what one
+ * launch addresses: COGDL_HIP_ERANGE.  A pointer not aligned to 4 bytes, or z1 / z2 / acc aligned to less than the lane width
+ * the geometry rule picks from x and out (at most 16 bytes): COGDL_HIP_EALIGN.
+ * workspace: cogdl_hip_csr_spmm_workspace_bytes(nnz, k, COGDL_HIP_F32) bytes (NULL: rows of any length are summed
+ * sequentially).  Launches on `stream`; no XCD plan, no sweep layout, no 16-bit operands.
+ * ------------------------------------------------------------------------------------------------------------------- */
+COGDL_API int cogdl_hip_csr_filter_step(const int32_t *rowptr, const int32_t *colind, const void *val, const void *x, void *out,
+                              int64_t n, int64_t k, int64_t nnz, int dtype, float a, float b, const void *z1, float c1,
+                              const void *z2, float c2, const float *dst_scale, void *acc, float d, void *workspace,
+                              size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -174,6 +174,18 @@ COGDL_HOST_API int cogdl_host_sort_pool_fwd(const float *x, const int32_t *ptr, 
 COGDL_HOST_API int cogdl_host_sort_pool_bwd(const float *grad, const int32_t *idx, int64_t N, int64_t B, int64_t F, int64_t k,
                                             float *grad_x);
 
+/* One step of a polynomial graph filter; the host twin of cogdl_hip_csr_filter_step (include/cogdl_hip.h, where the contract
+ * is spelled out): same arguments minus workspace and stream, all pointers host memory, dtype 0 (fp32) only.  An OpenMP loop
+ * over the rows; every row's sum is sequential fp32 in CSR order and the epilogue follows the header's statement order with
+ * separately rounded products and sums, so for equal inputs it returns EXACTLY the GPU's arrays in every row of at most the
+ * long-row threshold (cogdl_hip_long_row_threshold) edges; a longer row's sum is re-associated on the GPU and agrees to
+ * fp32 summation error.  The result does not depend on the number of threads.  The aliasing rules are the GPU's
+ * (COGDL_HOST_EINVAL); a malformed rowptr or a column id outside [0, n): COGDL_HOST_ERANGE, nothing is read out of bounds. */
+COGDL_HOST_API int cogdl_host_csr_filter_step(const int32_t *rowptr, const int32_t *colind, const float *val, const float *x,
+                                              float *out, int64_t n, int64_t k, int64_t nnz, int dtype, float a, float b,
+                                              const float *z1, float c1, const float *z2, float c2, const float *dst_scale,
+                                              float *acc, float d);
+
 #ifdef __cplusplus
 }
 #endif
