@@ -212,6 +212,7 @@ HOST_SIGNATURES = {
 }
 
 EUNSUPPORTED = 7  # COGDL_HIP_EUNSUPPORTED
+EALIGN = 3        # COGDL_HIP_EALIGN
 DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 _hip = None

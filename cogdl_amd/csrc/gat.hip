@@ -104,12 +104,26 @@ __global__ void edge_dropout_mask_kernel(float *__restrict__ mask, int64_t nnz, 
     for (int h = 0; h < heads; ++h) mask[e * heads + h] = ((bits >> h) & 1ull) ? d.scale : 0.f;
 }
 
+// The geometry is chosen at launch from the alignment of feat / out / grad_out / grad_feat, and narrower lanes can need MORE
+// scratch: H x F = 64 fp32 columns are 16 lanes of 4 floats on 16-byte operands and 64 lanes of 1 float on an operand that starts
+// 4 bytes into its allocation -- 96 against 192 floats per piece record.  A query cannot see the operands: it answers for the
+// worst of the alignments they can have (16, 8, 4 and, for 16-bit elements, 2 bytes).
+template <class F>
+size_t worst_alignment(int elem_bytes, F bytes_at) {
+    size_t need = 0;
+    for (int align = 16; align >= elem_bytes; align >>= 1) need = std::max(need, (size_t)bytes_at(align));
+    return need;
+}
+
 }  // namespace
 
 extern "C" size_t cogdl_hip_gat_fwd_workspace_bytes(int64_t nnz, int64_t h, int64_t f, int dtype) {
     if (nnz <= 0 || h <= 0 || f <= 0) return 0;
-    const RowGeometry g = gat_fwd_geometry(h, f, dtype == COGDL_HIP_F32 ? 4 : 2, 16);
-    return rowreduce_workspace_bytes(nnz, g.tiles * (g.vec + 2) * g.lpr);
+    const int eb = dtype == COGDL_HIP_F32 ? 4 : 2;
+    return worst_alignment(eb, [&](int align) {
+        const RowGeometry g = gat_fwd_geometry(h, f, eb, align);
+        return rowreduce_workspace_bytes(nnz, g.tiles * (g.vec + 2) * g.lpr);
+    });
 }
 
 extern "C" int cogdl_hip_gat_fwd(const int32_t *rowptr, const int32_t *colind, const float *attn_row,
@@ -140,8 +154,8 @@ extern "C" int cogdl_hip_gat_dropout_fwd(const int32_t *rowptr, const int32_t *c
 extern "C" size_t cogdl_hip_gat_bwd_workspace_bytes(int64_t v, int64_t n_src, int64_t h, int64_t f, int64_t nnz,
                                                     int dtype) {
     if (h <= 0 || f <= 0) return 256;
-    const GatBwdGeometry g = gat_bwd_geometry(h, f, 16, dtype == COGDL_HIP_F32 ? 4 : 2);
-    return bwd_layout(g, v, n_src, h, nnz).total + 256;
+    const int eb = dtype == COGDL_HIP_F32 ? 4 : 2;
+    return worst_alignment(eb, [&](int align) { return bwd_layout(gat_bwd_geometry(h, f, align, eb), v, n_src, h, nnz).total; }) + 256;
 }
 
 extern "C" int cogdl_hip_gat_bwd(const int32_t *rowptr, const int32_t *colind, const int32_t *colptr,
@@ -173,8 +187,11 @@ extern "C" int cogdl_hip_gat_dropout_bwd(const int32_t *rowptr, const int32_t *c
 // ---- XCD-partitioned plans (rowreduce.h: virtual rows) ------------------------------------------------------------------
 extern "C" size_t cogdl_hip_gat_fwd_xcd_workspace_bytes(int64_t n_parts, int64_t h, int64_t f, int dtype) {
     if (h <= 0 || f <= 0) return 256;
-    const RowGeometry g = gat_fwd_geometry(h, f, dtype == COGDL_HIP_F32 ? 4 : 2, 16);
-    return vrows_workspace_bytes(n_parts, g.tiles * (g.vec + 2) * g.lpr);
+    const int eb = dtype == COGDL_HIP_F32 ? 4 : 2;
+    return worst_alignment(eb, [&](int align) {
+        const RowGeometry g = gat_fwd_geometry(h, f, eb, align);
+        return vrows_workspace_bytes(n_parts, g.tiles * (g.vec + 2) * g.lpr);
+    });
 }
 
 extern "C" int cogdl_hip_gat_fwd_xcd(const cogdl_hip_vrows *plan, const float *attn_row, const float *attn_col,
@@ -218,8 +235,10 @@ BwdXcdLayout bwd_xcd_layout(const GatBwdGeometry &g, int64_t v, int64_t h, int64
 extern "C" size_t cogdl_hip_gat_bwd_xcd_workspace_bytes(int64_t v, int64_t h, int64_t f, int64_t n_parts_row,
                                                         int64_t n_parts_col, int dtype) {
     if (h <= 0 || f <= 0) return 256;
-    const GatBwdGeometry g = gat_bwd_geometry(h, f, 16, dtype == COGDL_HIP_F32 ? 4 : 2);
-    return bwd_xcd_layout(g, v, h, n_parts_row, n_parts_col).total + 256;
+    const int eb = dtype == COGDL_HIP_F32 ? 4 : 2;
+    return worst_alignment(eb, [&](int align) {
+        return bwd_xcd_layout(gat_bwd_geometry(h, f, align, eb), v, h, n_parts_row, n_parts_col).total;
+    }) + 256;
 }
 
 extern "C" int cogdl_hip_gat_bwd_xcd(const cogdl_hip_vrows *plan_csr, const cogdl_hip_vrows *plan_csc,

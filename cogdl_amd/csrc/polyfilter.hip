@@ -6,11 +6,14 @@
 // This is what the spectral propagation of ProNE and the heat-kernel / PPR / Gaussian filters around it iterate
 // (cogdl/utils/prone_utils.py:26-176: a Chebyshev recurrence on an [N, F] matrix; unfused, every sparse product is followed
 // by 2-5 elementwise passes over [N, F] tensors).  The functor IS csr_spmm's (spmm_op.h: SpmmOp, EXACT, no epilogue) with
-// another row_end, launched with the geometry spmm_auto picks for csr_spmm at this width: the t of every row is the t
-// cogdl_hip_csr_spmm computes for the same operands, bit for bit, long rows included -- the engine's long-row path only
-// merges states, and the combine kernel finishes a long row through the same row_end.  Every product and every sum of the
-// epilogue is a separately rounded fp32 operation, left to right as written (-ffp-contract=off, no fmaf); an absent
-// operand is never read and its term is skipped, not multiplied by zero.  fp32 only; no XCD plan, no sweep layout.
+// another row_end, launched with the geometry spmm_auto picks for csr_spmm at this width and the alignment of the least
+// aligned of x / out / z1 / z2 / acc: the t of every row up to the exact-row bound is the t cogdl_hip_csr_spmm computes for the
+// same operands, bit for bit; a long row's too while z1 / z2 / acc are at least as aligned as x / out (the same geometry: the
+// engine's long-row path only merges states, and the combine kernel finishes a long row through the same row_end) -- a less
+// aligned z1 / z2 / acc narrows the lanes, the pieces of a long row are cut per lane group, and its sum is re-associated.
+// Every product and every sum of the epilogue is a separately rounded fp32 operation, left to right as written
+// (-ffp-contract=off, no fmaf); an absent operand is never read and its term is skipped, not multiplied by zero.  fp32
+// only; no XCD plan, no sweep layout.
 #include "spmm_op.h"
 
 namespace cogdl {
@@ -91,10 +94,12 @@ static int filter_lpr(const FilterArgs &a, int lpr, void *ws, size_t wsb, hipStr
 
 template <int WMODE>
 static int filter_auto(const FilterArgs &a, void *ws, size_t wsb, hipStream_t s) {
-    // csr_spmm's own rule for these x / out (spmm_op.h: spmm_auto with narrow groups, no plan)
-    const RowGeometry g = spmm_geometry(a.k, a.k, (int)sizeof(float), pointer_alignment(a.x, a.out), true, false);
-    const size_t lane_bytes = (size_t)g.vec * sizeof(float);
-    if (!aligned_to(a.f.z1, lane_bytes) || !aligned_to(a.f.z2, lane_bytes) || !aligned_to(a.f.acc, lane_bytes)) return COGDL_HIP_EALIGN;
+    // csr_spmm's own rule (spmm_op.h: spmm_auto with narrow groups, no plan) for the least aligned of EVERY table a lane
+    // touches with load_vec / store_vec: x and out, and z1 / z2 / acc where present (NULL is aligned to anything).  An
+    // operand that starts mid-allocation narrows the lanes.  A row up to the exact-row bound is one sequential sum at every
+    // width; the pieces of a longer row follow the number of lane groups (rowreduce.h), so only there can the width show.
+    const int align = std::min(pointer_alignment(a.x, a.out), std::min(pointer_alignment(a.f.z1, a.f.z2), pointer_alignment(a.f.acc, nullptr)));
+    const RowGeometry g = spmm_geometry(a.k, a.k, (int)sizeof(float), align, true, false);
     switch (g.vec) {
         case 4: return filter_lpr<4, WMODE>(a, g.lpr, ws, wsb, s);
         case 2: return filter_lpr<2, WMODE>(a, g.lpr, ws, wsb, s);

@@ -145,12 +145,15 @@ class _HeadProjections(torch.autograd.Function):
             # both projections in one pass over feat (cogdl_hip_head_projection_fwd): torch's form is two broadcast products
             # into [N, H, F] fp32 temporaries and two reductions -- 0.24 ms of an 11.2 ms GAT step on the Reddit-shaped graph
             f3 = feat.contiguous()
+            # (bound to locals: a temporary copy of a strided a_l would go back to the caching allocator as soon as its address
+            #  is taken, and the copy of a_r would most likely reuse its block before the launch)
+            al, ar = a_l.detach().contiguous(), a_r.detach().contiguous()
             n, h, f = f3.shape
             h_l = torch.empty((n, h), dtype=torch.float32, device=feat.device)
             h_r = torch.empty_like(h_l)
             with _lib.on_device(feat.device):
-                rc = _lib.hip().cogdl_hip_head_projection_fwd(_lib.ptr(f3), _lib.DTYPE_CODE[f3.dtype], _lib.ptr(a_l.detach().contiguous()),
-                                                              _lib.ptr(a_r.detach().contiguous()), _lib.ptr(h_l), _lib.ptr(h_r), n, h, f,
+                rc = _lib.hip().cogdl_hip_head_projection_fwd(_lib.ptr(f3), _lib.DTYPE_CODE[f3.dtype], _lib.ptr(al), _lib.ptr(ar),
+                                                              _lib.ptr(h_l), _lib.ptr(h_r), n, h, f,
                                                               _lib.stream_of(f3))
             _lib.check(rc, "head_projection_fwd")
             return h_l, h_r

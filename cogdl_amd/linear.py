@@ -41,20 +41,23 @@ def linear_wgrad(x, grad_out, want_bias=True):
 
 
 EUNSUPPORTED = _lib.EUNSUPPORTED  # shape outside the hand-written kernel's coverage: torch's product is used
+EALIGN = _lib.EALIGN              # an operand that starts mid-allocation (x off its 16-byte lanes): likewise
+_DECLINED = (EUNSUPPORTED, EALIGN)
 
 
 def tall_skinny_matmul(x, w, bias, w_is_n_by_k):
     """x[R, K] . B (+ bias) through cogdl_hip_linear_fwd_f32, B = w^T (w [N, K]) or w ([K, N]); None if the kernel
-    declines the shape (the caller then uses torch's own product)."""
+    declines the shape or the operands' alignment (the caller then uses torch's own product)."""
     dev = x.device
     x, w = x.contiguous(), w.contiguous()
+    bias = None if bias is None else bias.contiguous()  # (read through a raw pointer like x and w: a strided view would be read as dense)
     rows, k = x.shape
     n = w.shape[0] if w_is_n_by_k else w.shape[1]
     out = torch.empty((rows, n), dtype=torch.float32, device=dev)
     with _lib.on_device(dev):
         rc = _lib.hip().cogdl_hip_linear_fwd_f32(_lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(out), rows, k, n,
                                                  1 if w_is_n_by_k else 0, _lib.stream_of(x))
-    if rc == EUNSUPPORTED:
+    if rc in _DECLINED:
         return None
     _lib.check(rc, "linear_fwd")
     return out
@@ -95,6 +98,7 @@ def tall_skinny_matmul_16(x, w, bias, w_is_n_by_k, out_dtype=torch.bfloat16):
     declines the shape."""
     dev = x.device
     x, w = x.contiguous(), w.contiguous()
+    bias = None if bias is None else bias.contiguous()  # (read through a raw pointer like x and w: a strided view would be read as dense)
     rows, k = x.shape
     n = w.shape[0] if w_is_n_by_k else w.shape[1]
     out = torch.empty((rows, n), dtype=out_dtype, device=dev)
@@ -102,7 +106,7 @@ def tall_skinny_matmul_16(x, w, bias, w_is_n_by_k, out_dtype=torch.bfloat16):
         rc = getattr(_lib.hip(), _HALF_ENTRY[out_dtype])(_lib.ptr(x), _lib.DTYPE_CODE[x.dtype], _lib.ptr(w), _lib.DTYPE_CODE[w.dtype],
                                                          _lib.ptr(bias), _lib.ptr(out), rows, k, n, 1 if w_is_n_by_k else 0,
                                                          _lib.stream_of(x))
-    if rc == EUNSUPPORTED:
+    if rc in _DECLINED:
         return None
     _lib.check(rc, "linear_fwd_16")
     return out

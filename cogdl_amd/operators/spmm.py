@@ -59,6 +59,16 @@ def _check_csr(rowptr, colind, x):
         raise _lib.BackendError("unsupported dtype %s" % x.dtype)
 
 
+def _need_aligned(what, nbytes, **operands):
+    """The launches over a plan or a sweep layout take operands aligned to their widest lane (csrc/spmm.hip); whether a call
+    gets one is xcdplan's decision (xcdplan.aligned), and a caller of the raw entries makes the same one: csr_spmm_raw takes a
+    dense operand at any element offset, `out=` included."""
+    for name, t in operands.items():
+        if not xcdplan.aligned(t, nbytes):
+            raise _lib.BackendError("%s: %s starts %d bytes past a multiple of %d, and this launch reads it in %d-byte lanes; "
+                                    "csr_spmm_raw takes the operand as it is" % (what, name, t.data_ptr() % nbytes, nbytes, nbytes))
+
+
 def csr_spmm_raw(rowptr, colind, val, x, variant=-1, out=None, split_long_rows=True, row_order=None):
     """One cogdl_hip_csr_spmm launch on the current stream (no autograd).  With `out` given the result is
     accumulated into it (out += A x, cogdl_hip_csr_spmm_acc).  row_order: an int32 permutation of the rows, the row blocks'
@@ -132,6 +142,7 @@ def csr_spmm_xcd_raw(xplan, val, x, out=None):
             raise _lib.BackendError("accumulation target must be a contiguous [%d, %d] %s tensor" % (m, k, x.dtype))
     else:
         out = torch.empty((m, k), dtype=x.dtype, device=dev)
+    _need_aligned("csr_spmm_xcd", 16, x=x, out=out)
     code = _lib.DTYPE_CODE[x.dtype]
     ws, ws_bytes = _lib.workspace("cogdl_hip_csr_spmm_xcd_workspace_bytes", dev, xplan.n_parts, k, code)
     with _lib.on_device(dev):
@@ -151,6 +162,7 @@ def csr_spmm_sweep_raw(csc, val, x):
     if x.dim() != 2 or x.dtype != torch.float32 or x.shape[0] != csc.m:
         raise _lib.BackendError("csr_spmm_sweep: the dense operand must be a float32 [%d, k] tensor" % csc.m)
     x = x.contiguous()
+    _need_aligned("csr_spmm_sweep", 8, x=x)
     k = x.shape[1]
     sp = sweepplan.of(csc, k, x.dtype)
     if val is not None:
@@ -192,6 +204,7 @@ def csr_spmm_sweep_forward_raw(sp, parts, rowptr, colind, val, x):
     if parts.dtype != torch.int64 or parts.numel() != _plan.FINGERPRINT_PARTS or not parts.is_contiguous():
         raise _lib.BackendError("csr_spmm_sweep_forward: the hash partials must be a contiguous int64 [%d] tensor" % _plan.FINGERPRINT_PARTS)
     x, rowptr, colind = x.contiguous(), rowptr.contiguous(), colind.contiguous()
+    _need_aligned("csr_spmm_sweep_forward", 8, x=x)  # (asked BEFORE the first of the two launches: neither goes out alone)
     val_p = None
     if val is not None:
         if val.numel() != nnz:

@@ -58,6 +58,10 @@ def gather_rows_by_id(src, ids, out=None, flag_word=None):
         return out
     if row_bytes % 4:
         raise _lib.BackendError("gather_rows_by_id: rows of %d bytes (must be a multiple of 4)" % row_bytes)
+    for name, t in (("src", src), ("out", out)):  # (16-bit rows at an odd element offset: the kernel copies 4-byte words)
+        if t.data_ptr() % 4:
+            raise _lib.BackendError("gather_rows_by_id: %s starts %d bytes past a 4-byte boundary; the kernel copies 4-byte "
+                                    "words, so %s must be 4-byte aligned" % (name, t.data_ptr() % 4, name))
     if flag_word is None:
         bad = torch.zeros(1, dtype=torch.int32, device=dev)
         flag_ptr = _lib.ptr(bad)

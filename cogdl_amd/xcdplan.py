@@ -273,6 +273,14 @@ def forced():
     return MODE == "force"
 
 
+def aligned(t, nbytes):
+    """Does the dense operand start on a multiple of `nbytes`?  A contiguous view into a larger allocation (a slice of a flat
+    parameter buffer, a narrow of a packed batch, an upstream gradient that is one) need not.  The plan kernels take 16-byte
+    operands and the sweep kernels 8-byte ones (csrc/spmm.hip), the ordinary launch narrows its lanes instead: such an operand
+    is a reason for the ordinary launch, decided here and never found out from a status code."""
+    return t.data_ptr() % nbytes == 0
+
+
 def spmm_split(fp, rowptr, m, nnz, x):
     """csr_spmm, either direction: the row length to cut at, or None (the ordinary launch).  fp: the structure's Fingerprint if its
     key counts as known to this call, else None.
@@ -283,8 +291,9 @@ def spmm_split(fp, rowptr, m, nnz, x):
               Reddit-shaped graph (profiles/r06_xcd_spmm_split.txt): bf16 F = 64 1524 -> 1316 us, F = 128 3241 -> 2291 us; at
               split 64 / 1024: 1386 / 1345 us.  (Before the hub rows' part records were merged by whole workgroups -- rowreduce.h:
               rowreduce_vcombine_kernel -- the same plan LOST: 1512 -> 1638 us, profiles/r06_xcd_quick.txt.)
-      else S  cut at E whatever the dtype (rows up to it stay whole and sequential, as in the ordinary launch)."""
-    if x.dim() != 2 or x.dtype not in _lib.DTYPE_CODE:
+      else S  cut at E whatever the dtype (rows up to it stay whole and sequential, as in the ordinary launch).
+    An x that is not 16-byte aligned: None in every mode, "force" included (see aligned)."""
+    if x.dim() != 2 or x.dtype not in _lib.DTYPE_CODE or not aligned(x, 16):
         return None
     n_src, row_bytes = x.shape[0], x.shape[1] * x.element_size()
     hub = wanted(m, nnz, n_src, row_bytes)
@@ -342,6 +351,8 @@ def spmm_backward_sweep(csc, grad_out, round_rows=None):
         return False
     if grad_out.dim() != 2 or grad_out.dtype != torch.float32 or grad_out.shape[1] * grad_out.element_size() != SWEEP_ROW_BYTES:
         return False
+    if not aligned(grad_out, 8):  # (the sweep kernel's float2 lanes; the ordinary launch narrows instead)
+        return False
     from . import sweepplan
 
     n_src = grad_out.shape[0]
@@ -386,8 +397,8 @@ def spmm_forward_sweep(fp, rowptr, colind, x, round_rows=None):
     nnz, n_src) and the call hashed into device memory (Fingerprint.dev); the layout has no row above the exact-row bound (the
     sweep reduces every row sequentially) and at most SWEEP_FORWARD_MAX_OUT_OF_ORDER of its edges behind their row's
     running maximum.  Never waits, never reads back."""
-    if fp is None or getattr(fp, "dev", None) is None or x.dim() != 2:
-        return None
+    if fp is None or getattr(fp, "dev", None) is None or x.dim() != 2 or not aligned(x, 8):
+        return None  # (an x off the float2 lanes of BOTH guarded launches: refused here, before either is enqueued)
     if not spmm_forward_sweep_shape(rowptr.numel() - 1, colind.numel(), x.shape[0], x.shape[1], x.dtype, round_rows):
         return None
     from . import sweepplan

@@ -552,7 +552,10 @@ COGDL_API int cogdl_hip_disen_route_bwd_z(const int32_t *srcptr, const int32_t *
  * Forward also emits edge_max/edge_sum [v,H] (row max of s and sum exp(s-max)), which the
  * backward consumes like the reference's ctx.save_for_backward does (fused_gat.py:20).
  * Forward workspace (optional): cogdl_hip_gat_fwd_workspace_bytes -- hub rows are then split over whole
- * workgroups and their (max, sum, acc) states merged like flash-attention blocks.
+ * workgroups and their (max, sum, acc) states merged like flash-attention blocks.  The launch picks its lane width from the
+ * alignment of feat / out (backward: grad_out / grad_feat too), and narrower lanes need larger piece records: the four
+ * workspace queries of this operator answer for the least aligned operands an element type allows, so an operand that
+ * starts mid-allocation never meets COGDL_HIP_EWORKSPACE with a workspace of the queried size.
  * Backward needs the CSC view (colptr,rowind from cogdl_hip_csr2csc), the forward
  * output and a workspace of cogdl_hip_gat_bwd_workspace_bytes(v, n_src, h, f, nnz, dtype) bytes (D[v,h], the per-tile
  * partials of the tiled shapes, plus the long-row scratch of its two passes; a workspace without the latter disables
@@ -1118,15 +1121,19 @@ COGDL_API int cogdl_hip_sort_pool_bwd(const float *grad, const int32_t *idx, int
  *     y        = y + c2 * z2[i,:]                      (only when z2 is given)
  *     out[i,:] = y
  *     acc[i,:] = acc[i,:] + d * y                      (only when acc is given)
- * Arithmetic: t is cogdl_hip_csr_spmm's sum for the same operands, bit for bit, long rows included (the same functor with
- * the launch geometry csr_spmm takes at this k and these x / out).  Every product and every sum of the epilogue is a
- * separately rounded fp32 operation, left to right as written (no fused multiply-add).  An absent operand is never read and
- * its term is skipped, not multiplied by zero.  A row without edges has t = 0 and still gets its epilogue.
+ * Arithmetic: t is cogdl_hip_csr_spmm's sum for the same operands, bit for bit, on every row of at most
+ * cogdl_hip_exact_row_edges(nnz) edges (one sequential sum, whatever the lanes).  The launch is the same functor with the
+ * geometry csr_spmm takes at this k for the LEAST aligned of x, out, z1, z2 and acc, so an operand that starts mid-allocation
+ * narrows the lanes instead of failing the call.  A longer row is summed in pieces whose cut follows the number of lane groups,
+ * hence the lane width: it equals csr_spmm's sum for these x / out bit for bit while z1, z2 and acc are at least as aligned as
+ * x and out (the geometries are then the same), and up to re-association of the pieces otherwise.  Every product and every
+ * sum of the epilogue is a separately rounded fp32 operation, left to right as written (no fused multiply-add).  An absent
+ * operand is never read and its term is skipped, not multiplied by zero.  A row without edges has t = 0 and still gets its
+ * epilogue.
  * Aliasing: out may be z1 or z2, acc may be z1 or z2 (each lane reads its columns before it writes them).  out overlapping
  * x or acc, acc overlapping x, or a z that overlaps out / acc without being it: COGDL_HIP_EINVAL.
  * dtype != COGDL_HIP_F32: COGDL_HIP_EUNSUPPORTED.  n == 0 or k == 0: success, nothing launched.  k or nnz beyond what one
- * launch addresses: COGDL_HIP_ERANGE.  A pointer not aligned to 4 bytes, or z1 / z2 / acc aligned to less than the lane width
- * the geometry rule picks from x and out (at most 16 bytes): COGDL_HIP_EALIGN.
+ * launch addresses: COGDL_HIP_ERANGE.  A pointer not aligned to 4 bytes: COGDL_HIP_EALIGN.
  * workspace: cogdl_hip_csr_spmm_workspace_bytes(nnz, k, COGDL_HIP_F32) bytes (NULL: rows of any length are summed
  * sequentially).  Launches on `stream`; no XCD plan, no sweep layout, no 16-bit operands.
  * ------------------------------------------------------------------------------------------------------------------- */
