@@ -37,10 +37,20 @@
 // compiler does not see as memory operations; what it must not do with a register in flight is said through operands: a
 // slot is an output of its request, an in/out operand of its wait (no read moves above it), and every slot and the words on
 // their way are operands of the drain (no register is reused under a load that has not landed).  After every compiler or
-// flag change look at the ISA: no instruction may touch a slot between its request and its wait (profiles/sweep_pipeline.txt).
-// The layout words of 64 edges sit in one VGPR each; the next 64 are requested, on the same counter, right after the batch
-// that took the current ones up, and are long retired (64 edges of counted waits) when their turn comes.  With them behind
-// the ring a wait retires up to three gathers instead of one for kSweepRing edges: once in 64.
+// flag change look at the ISA: no instruction may touch a slot between its request and its wait (profiles/sweep_issue.txt).
+// The layout words of 64 edges sit in one VGPR each; the next 64 are requested, on the same counter, at the word turn (the
+// place in a batch from which the requests belong to the next 64 edges), and are long retired (64 edges of counted waits)
+// when their turn comes.  With them behind the ring a wait retires up to three gathers instead of one for kSweepRing edges:
+// once in 64.
+// The instruction stream.  The walk is bound by instruction issue, not by the fabric (profiles/sweep_issue.txt: the issue
+// cycles of a SIMD's four waves add up to the launch's length, every instruction costs its wave about four cycles), so an
+// edge is held to about 16 instructions (it was 32):
+//   request    s_lshl (word << 9, the row's byte offset) + buffer_load with that scalar offset (sweep_request)
+//   words      two v_readlane where the gather is requested; they stay in the SGPRs the slot's fold reads kSweepRing edges
+//              later (a static rotation over the batch: no copies), + one s_add for the lane
+//   row kind   s_cmp + s_cbranch, twice (register row / LDS row)
+//   fold       one v_pk_mul, then s_lshr, s_set_gpr_idx_on, two v_add ON the indexed registers, s_set_gpr_idx_off (sweep_fold)
+//   end test   none in a batch that lies inside the group; the group's last, partial batch runs a tested copy of the body
 // Depth.  More in flight is NOT better here: every gather in flight holds a line of the XCD's L2 that the walk wants for
 // rows other waves are about to ask for.  512 waves x 8 rows x 512 bytes are 2 of an XCD's 4 MiB: at depth 8 the launch's L2 hit
 // rate falls from 0.30 to 0.21 and the launch is 12 % SLOWER than the batches of 8 it replaced (which drained to nothing while
@@ -52,7 +62,7 @@ namespace cogdl {
 
 constexpr int kSweepRows = 48;       // rows per wave (32 in registers, 16 in LDS); 4 waves per SIMD
 constexpr int kSweepWavesPerCu = 16;
-constexpr int kSweepUnroll = 8;      // edges per unrolled batch (one v_readlane pass over the words at hand)
+constexpr int kSweepUnroll = 8;      // edges per unrolled batch (the words of its edges rotate through 8 SGPR pairs)
 constexpr int kSweepRing = 4;        // gathers a wave keeps in flight (measured: 2, 4, 8 -- see the header comment)
 
 struct SweepArgs {
@@ -64,6 +74,7 @@ struct SweepArgs {
     int64_t m, n_groups;
     int r;          // rows per group (<= kSweepRows)
     uint32_t row_bytes;
+    uint32_t table_bytes;  // the gathered table's size, for the descriptor's range check (0 for a table of 2^32 bytes: sweep_args)
 };
 
 typedef float SweepF32x32 __attribute__((ext_vector_type(32)));
@@ -71,28 +82,74 @@ constexpr int kSweepRegRows = 32;                          // rows whose state i
 constexpr int kSweepLdsRows = kSweepRows - kSweepRegRows;  // ... and the rest: 8 bytes per lane and row in LDS (8 KB per wave)
 
 // The states of a wave's kSweepRows rows, two columns per lane.  The local row of an edge is wave-uniform: rows 0..31 live in
-// two register tuples and are picked with an indexed register move, rows 32..47 in the wave's own LDS slab (every lane reads
+// two register tuples and are picked with the register index mode, rows 32..47 in the wave's own LDS slab (every lane reads
 // and writes only its own words: no barrier).  (A dynamically indexed ARRAY goes to scratch memory; a `switch` over constant
 // indices in an unrolled batch, and a third register tuple, each made the register allocator spill.)
 // Fold one gathered row into the state of local row `lr`.
+// A register row is added to IN PLACE: both tuples sit on fixed registers (v[64:95], v[96:127]: the upper half of the kernel's
+// 128) and one s_set_gpr_idx_on (SRC0 | DST) makes `v_add_f32 v64, v64, t` read and write v[64 + lr].  The index mode is on for
+// these two instructions only, inside one statement; it goes through m0.  The product w * x is rounded by a v_mul of its own
+// in front (-ffp-contract=off), the sum by the v_add: the same two roundings as `s + w * x`.
 template <bool WEIGHTED>
-__device__ __forceinline__ void sweep_fold(SweepF32x32 &lo0, SweepF32x32 &lo1, float2 *hi, int lr, float w, float2 v) {
-    if (lr < kSweepRegRows) {
-        const float s0 = lo0[lr], s1 = lo1[lr];
-        lo0[lr] = WEIGHTED ? s0 + w * v.x : s0 + v.x;
-        lo1[lr] = WEIGHTED ? s1 + w * v.y : s1 + v.y;
-    } else {
-        float2 *p = hi + (lr - kSweepRegRows) * kWave;
+__device__ __forceinline__ void sweep_fold(SweepF32x32 &lo0, SweepF32x32 &lo1, float2 *hi, uint32_t word, float w, float2 v) {
+    // (two tests, not if / else: the compiler lays a wave-uniform if / else out through a mask in vcc, five instructions)
+    const float t0 = WEIGHTED ? w * v.x : v.x, t1 = WEIGHTED ? w * v.y : v.y;
+    if (word < ((uint32_t)kSweepRegRows << 24)) {
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"  // ("clobber list contains reserved registers: m0" -- it is written here)
+        asm volatile("s_set_gpr_idx_on %2, gpr_idx(SRC0,DST)\n\t"
+                     "v_add_f32_e32 v64, v64, %3\n\t"
+                     "v_add_f32_e32 v96, v96, %4\n\t"
+                     "s_set_gpr_idx_off"
+                     : "+{v[64:95]}"(lo0), "+{v[96:127]}"(lo1)
+                     : "s"(word >> 24), "v"(t0), "v"(t1)
+                     : "m0");
+#pragma clang diagnostic pop
+    }
+    if (word >= ((uint32_t)kSweepRegRows << 24)) {
+        float2 *p = hi + ((int)(word >> 24) - kSweepRegRows) * kWave;
         const float2 s = *p;
-        *p = WEIGHTED ? make_float2(s.x + w * v.x, s.y + w * v.y) : make_float2(s.x + v.x, s.y + v.y);
+        *p = make_float2(s.x + t0, s.y + t1);
     }
 }
 
-// One gather of the ring: the 512-byte row at byte offset `off` (+ the lane's own 8 bytes) of the table, requested into `slot`.
+// Zero both tuples where they live.  (As two plain assignments the equal values become ONE tuple elsewhere and 32 register
+// copies into each pinned one, at every group's start.)
+__device__ __forceinline__ void sweep_zero(SweepF32x32 &lo0, SweepF32x32 &lo1) {
+    asm volatile(".set .Lsweep_zero_reg, 64\n\t"
+                 ".rept 64\n\t"
+                 "v_mov_b32_e32 v[.Lsweep_zero_reg], 0\n\t"
+                 ".set .Lsweep_zero_reg, .Lsweep_zero_reg + 1\n\t"
+                 ".endr"
+                 : "={v[64:95]}"(lo0), "={v[96:127]}"(lo1));
+}
+
+// The table as a buffer descriptor, built once per launch (wave-uniform values only).  The range check of a raw buffer sees
+// the scalar offset too (measured on gfx950: with `num_records` of one row every row but the first reads as zero), so
+// `num_records` is the table's size in bytes and an offset beyond the table loads zero instead of faulting.  32 bits: a table
+// of exactly 2^23 rows ends at byte 2^32, one more than the field can say -- that table alone keeps the global_load request
+// (SweepArgs::wide; 2^23 rows are the most a layout names, cogdl_amd/sweepplan.py: MAX_TABLE_ROWS).
+typedef int SweepRsrc __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ SweepRsrc sweep_table(const void *x, uint32_t bytes) {
+    const uint64_t base = (uint64_t)(uintptr_t)x;
+    SweepRsrc t;
+    t.x = (int)(uint32_t)base;
+    t.y = (int)(uint32_t)((base >> 32) & 0xffffu);  // (stride 0: a raw buffer)
+    t.z = (int)bytes;
+    t.w = 0x00020000;
+    return t;
+}
+
+// One gather of the ring: the 512-byte row named by the layout word `word` (+ the lane's own 8 bytes), requested into `slot`.
+// `word << 9` is the row's byte offset: the table has at most 2^23 rows, the local row in the top 8 bits falls out.  It is the
+// load's scalar offset (one s_lshl; the lane's offset is a VGPR that never changes); WIDE: a VALU add and a global_load.
 // The compiler takes `slot` for written when this returns; it is not, until sweep_wait has named it.
 typedef float SweepF32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void sweep_request(SweepF32x2 &slot, uint32_t off, const char *table) {
-    asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(slot) : "v"(off), "s"(table));
+template <bool WIDE>
+__device__ __forceinline__ void sweep_request(SweepF32x2 &slot, uint32_t word, uint32_t lane_off, const SweepRsrc &table, const char *x) {
+    static_assert(kWave * sizeof(float2) == 512, "word << 9");
+    if constexpr (WIDE) asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(slot) : "v"((word << 9) + lane_off), "s"(x));
+    else asm volatile("buffer_load_dwordx2 %0, %1, %2, %3 offen" : "=v"(slot) : "v"(lane_off), "s"(table), "s"(word << 9));
 }
 // Wait for the oldest gather of the ring and leave the kSweepRing - 1 younger ones in flight.  `slot` is an operand so that
 // no read of it can be moved above the wait.
@@ -127,14 +184,15 @@ __device__ __forceinline__ void sweep_words_turn(uint32_t &p, float &w, uint32_t
 // One wave per row group, four waves per workgroup; groups beyond one round of the grid are walked by the same waves,
 // grid-stride (correct, only less local).  Rows of 128 fp32 columns: one float2 per lane.
 // (The body of both kernels below: the unguarded one is this and nothing else.)
-template <bool WEIGHTED>
+template <bool WEIGHTED, bool WIDE>
 __device__ __forceinline__ void sweep_walk(const SweepArgs &a) {
     constexpr int UNROLL = kSweepUnroll;
     static_assert(UNROLL % kSweepRing == 0 && kWave % UNROLL == 0, "a slot is an edge's place in its batch, a batch never straddles the words at hand");
     typedef const __attribute__((address_space(4))) int32_t *ConstI32;
     const int lane = threadIdx.x & (kWave - 1);
     const uint32_t lane_off = (uint32_t)lane * (uint32_t)sizeof(float2);
-    const char *const table = reinterpret_cast<const char *>(a.x);
+    const char *const xb = reinterpret_cast<const char *>(a.x);
+    const SweepRsrc table = sweep_table(a.x, a.table_bytes);
     // (the group offsets are read-only for the launch and their index is wave-uniform: scalar loads, counted on lgkmcnt)
     const ConstI32 goff = (ConstI32)(uintptr_t)a.goff;
     __shared__ float2 slab[4][kSweepLdsRows][kWave];
@@ -142,7 +200,8 @@ __device__ __forceinline__ void sweep_walk(const SweepArgs &a) {
     const int64_t wave0 = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
     const int64_t n_waves = (int64_t)gridDim.x * 4;
     for (int64_t g = wave0; g < a.n_groups; g += n_waves) {  // (a wave past the last group exits)
-        SweepF32x32 lo0 = 0.f, lo1 = 0.f;
+        SweepF32x32 lo0, lo1;
+        sweep_zero(lo0, lo1);
 #pragma unroll
         for (int c = 0; c < kSweepLdsRows; ++c) hi[c * kWave] = make_float2(0.f, 0.f);
         const int start = goff[g];
@@ -157,51 +216,50 @@ __device__ __forceinline__ void sweep_walk(const SweepArgs &a) {
             sweep_words<WEIGHTED>(cp, cw, a.src, a.w, min(start + lane, last));
             sweep_words<WEIGHTED>(ncp, ncw, a.src, a.w, min(start + kWave + lane, last));
             sweep_words_landed<WEIGHTED>(cp, cw);
-            int cbase = start;
-            uint32_t p[UNROLL], np[UNROLL];
-            float w[UNROLL], nw[UNROLL];
+            int nbase = start + 2 * kWave;  // the words to ask for at the next turn
+            int k = 0;                      // the batch's place in the words at hand
+            // The words of an edge are read where its gather is requested and stay in the SGPRs that its fold reads
+            // kSweepRing edges later: P[q] / W[q] belong to the edges at place q of a batch, a static rotation without copies.
+            uint32_t P[UNROLL];
+            float W[UNROLL];
             SweepF32x2 v[kSweepRing];
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) {
-                p[u] = (uint32_t)__builtin_amdgcn_readlane((int)cp, u);
-                w[u] = WEIGHTED ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cw), u)) : 1.f;
-            }
             // Prologue: the first kSweepRing gathers.
 #pragma unroll
-            for (int u = 0; u < kSweepRing; ++u) sweep_request(v[u], (p[u] & 0xffffffu) * a.row_bytes + lane_off, table);
-            for (int e = start; e < end; e += UNROLL) {
-                int k = e + UNROLL - cbase;  // the next batch's place in the words at hand
-                const bool turn = k == kWave;
-                if (turn) {  // (requested 64 edges ago: the counted waits since have retired them, in order)
-                    sweep_words_turn(cp, cw, ncp, ncw);
-                    cbase += kWave;
-                    k = 0;
-                }
+            for (int u = 0; u < kSweepRing; ++u) {
+                P[u] = (uint32_t)__builtin_amdgcn_readlane((int)cp, u);
+                W[u] = WEIGHTED ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cw), u)) : 1.f;
+                sweep_request<WIDE>(v[u], P[u], lane_off, table, xb);
+            }
+            // Steady state: edge i waits for slot i % kSweepRing alone, is folded, and edge i + kSweepRing is requested into the
+            // slot the fold has just freed.  `tested`: the batch may reach past the group's end (its last one only).
+            int e = start;
+            auto batch = [&](auto tested) {
 #pragma unroll
                 for (int u = 0; u < UNROLL; ++u) {
-                    np[u] = (uint32_t)__builtin_amdgcn_readlane((int)cp, k + u);
-                    nw[u] = WEIGHTED ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cw), k + u)) : 1.f;
-                }
-                // Steady state: edge i waits for slot i % kSweepRing alone, is folded, and edge i + kSweepRing is requested into
-                // the slot the fold has just freed -- its words are further down this batch's or at the head of the next one's.
-#pragma unroll
-                for (int u = 0; u < UNROLL; ++u) {
+                    if (u == UNROLL - kSweepRing && k == kWave - UNROLL) {
+                        // The word turn: the requests from here on belong to the next 64 edges.  (Their words were requested
+                        // 64 edges ago: the counted waits since have retired them, in order.)  The words after those: two
+                        // more loads behind the ring's.  The counted wait stays what it is, so for the next kSweepRing edges a
+                        // wait retires up to three gathers instead of one -- once in 64 edges.
+                        sweep_words_turn(cp, cw, ncp, ncw);
+                        sweep_words<WEIGHTED>(ncp, ncw, a.src, a.w, min(nbase + lane, last));
+                        nbase += kWave;
+                        k = -UNROLL;
+                    }
                     SweepF32x2 &slot = v[u % kSweepRing];
                     sweep_wait(slot);
                     // (wave-uniform: a slot past the group's end is skipped, not folded as 0 * 0)
-                    if (e + u < end) sweep_fold<WEIGHTED>(lo0, lo1, hi, (int)(p[u] >> 24), w[u], make_float2(slot.x, slot.y));
-                    const uint32_t rq = u + kSweepRing < UNROLL ? p[(u + kSweepRing) % UNROLL] : np[(u + kSweepRing) % UNROLL];
-                    sweep_request(slot, (rq & 0xffffffu) * a.row_bytes + lane_off, table);
+                    if (!decltype(tested)::value || e + u < end) sweep_fold<WEIGHTED>(lo0, lo1, hi, P[u], W[u], make_float2(slot.x, slot.y));
+                    const int q = (u + kSweepRing) % UNROLL;
+                    P[q] = (uint32_t)__builtin_amdgcn_readlane((int)cp, k + u + kSweepRing);
+                    W[q] = WEIGHTED ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cw), k + u + kSweepRing)) : 1.f;
+                    sweep_request<WIDE>(slot, P[q], lane_off, table, xb);
                 }
-#pragma unroll
-                for (int u = 0; u < UNROLL; ++u) {
-                    p[u] = np[u];
-                    w[u] = nw[u];
-                }
-                // The words after those just taken up: two more loads behind the ring's.  The counted wait stays what it is, so
-                // for the next kSweepRing edges a wait retires up to three gathers instead of one -- once in 64 edges.
-                if (turn) sweep_words<WEIGHTED>(ncp, ncw, a.src, a.w, min(cbase + kWave + lane, last));
-            }
+                k += UNROLL;
+                e += UNROLL;
+            };
+            while (e + UNROLL <= end) batch(std::false_type{});  // every slot inside the group: no test per edge
+            if (e < end) batch(std::true_type{});
             sweep_drain(v, ncp, ncw);
         }
         // (rows of a partial last group that do not exist are never stored)
@@ -218,16 +276,26 @@ __device__ __forceinline__ void sweep_walk(const SweepArgs &a) {
     }
 }
 
-template <bool WEIGHTED>
+template <bool WEIGHTED, bool WIDE>
 __global__ __launch_bounds__(256, 4) void rowreduce_sweep_kernel(const SweepArgs a) {
-    sweep_walk<WEIGHTED>(a);
+    sweep_walk<WEIGHTED, WIDE>(a);
 }
 
 // The same walk, taken only if the guard says so (see the header comment); a wave that stands down has written nothing.
-template <bool WEIGHTED>
+template <bool WEIGHTED, bool WIDE>
 __global__ __launch_bounds__(256, 4) void rowreduce_sweep_guarded_kernel(const SweepArgs a, const HashGuard guard) {
     if (!guard_runs(guard)) return;
-    sweep_walk<WEIGHTED>(a);
+    sweep_walk<WEIGHTED, WIDE>(a);
+}
+
+// The arguments of either kernel for a table of n_src rows; -> WIDE, whether the table's end is beyond a descriptor's reach.
+inline bool sweep_args(SweepArgs &a, const int32_t *goff, const int32_t *src, const void *w, const void *x, void *out, int64_t m,
+                       int64_t n_src, int64_t n_groups, int r, int64_t k) {
+    const uint64_t bytes = (uint64_t)n_src * (uint64_t)k * sizeof(float);
+    const bool wide = bytes > 0xffffffffull;
+    a = SweepArgs{goff, (const uint32_t *)src, (const float *)w, (const float *)x, (float *)out, m, n_groups, r,
+                  (uint32_t)(k * sizeof(float)), wide ? 0u : (uint32_t)bytes};
+    return wide;
 }
 
 // Waves of one round on the current device (CU count x waves that fit), capped by tuning key 18 (tests: rows per round).

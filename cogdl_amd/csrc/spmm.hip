@@ -231,10 +231,13 @@ extern "C" int cogdl_hip_csr_spmm_sweep(const int32_t *goff, const int32_t *src,
         g_last_hip_error = (int)hipGetLastError();
         return COGDL_HIP_ELAUNCH;
     }
-    SweepArgs a{goff, (const uint32_t *)src, (const float *)w, (const float *)x, (float *)out, m, n_groups, r, (uint32_t)(k * sizeof(float))};
+    SweepArgs a;
+    const bool wide = sweep_args(a, goff, src, w, x, out, m, n_src, n_groups, r, k);
     const unsigned blocks = (unsigned)((std::min(waves, n_groups) + 3) / 4);
-    if (w) hipLaunchKernelGGL((rowreduce_sweep_kernel<true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((rowreduce_sweep_kernel<false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+    if (w && !wide) hipLaunchKernelGGL((rowreduce_sweep_kernel<true, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+    else if (w) hipLaunchKernelGGL((rowreduce_sweep_kernel<true, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+    else if (!wide) hipLaunchKernelGGL((rowreduce_sweep_kernel<false, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((rowreduce_sweep_kernel<false, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
     return launch_status();
 }
 
@@ -267,10 +270,13 @@ extern "C" int cogdl_hip_csr_spmm_sweep_guarded(const int32_t *goff, const int32
         g_last_hip_error = (int)hipGetLastError();
         return COGDL_HIP_ELAUNCH;
     }
-    SweepArgs a{goff, (const uint32_t *)src, (const float *)w, (const float *)x, (float *)out, m, n_groups, r, (uint32_t)(k * sizeof(float))};
+    SweepArgs a;
+    const bool wide = sweep_args(a, goff, src, w, x, out, m, n_src, n_groups, r, k);
     const unsigned blocks = (unsigned)((std::min(waves, n_groups) + 3) / 4);
-    if (w) hipLaunchKernelGGL((rowreduce_sweep_guarded_kernel<true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, guard);
-    else hipLaunchKernelGGL((rowreduce_sweep_guarded_kernel<false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, guard);
+    if (w && !wide) hipLaunchKernelGGL((rowreduce_sweep_guarded_kernel<true, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, guard);
+    else if (w) hipLaunchKernelGGL((rowreduce_sweep_guarded_kernel<true, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, guard);
+    else if (!wide) hipLaunchKernelGGL((rowreduce_sweep_guarded_kernel<false, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, guard);
+    else hipLaunchKernelGGL((rowreduce_sweep_guarded_kernel<false, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, guard);
     return launch_status();
 }
 
