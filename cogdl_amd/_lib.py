@@ -37,6 +37,8 @@ HIP_SIGNATURES = {
     "cogdl_hip_csr_spmm_sweep_round_rows": ([_i64, _i32], _i64),
     "cogdl_hip_csr_spmm_sweep": ([_vp] * 5 + [_i64, _i64, _i64, _i32, _i64, _i64, _i32, _vp], _i32),
     "cogdl_hip_csr_spmm_sweep_guarded": ([_vp] * 5 + [_i64, _i64, _i64, _i32, _i64, _i64, _i32, _vp, _u64, _i32, _vp], _i32),
+    "cogdl_hip_csr_spmm_sweep_rows": ([_vp] * 5 + [_i64, _i64, _i64, _i32, _i64, _i64, _i32, _vp, _i64, _vp], _i32),
+    "cogdl_hip_csr_spmm_sweep_rows_guarded": ([_vp] * 5 + [_i64, _i64, _i64, _i32, _i64, _i64, _i32, _vp, _i64, _vp, _u64, _i32, _vp], _i32),
     "cogdl_hip_csr_spmm_guarded": ([_vp] * 5 + [_i64, _i64, _i64, _i32, _vp, _u64, _i32, _vp, _sz, _vp], _i32),
     "cogdl_hip_gat_fwd_xcd_workspace_bytes": ([_i64, _i64, _i64, _i32], _sz),
     "cogdl_hip_gat_fwd_xcd": ([_vp] * 4 + [_f32, _f32, _u64] + [_vp] * 3 + [_i64, _i64, _i64, _i32, _vp, _sz, _vp], _i32),

@@ -25,6 +25,13 @@
 //   goff [n_groups + 1]   edge offsets of the groups
 //   src  [nnz]            per edge: gathered row (low 24 bits) | local row inside the group (high 8 bits)
 //   w    [nnz]            edge weights in layout order, or NULL
+//   rows [n_groups * r]   optional (SweepArgs::rows, template argument MAPPED): the output row of local row l of group g at
+//                         g * r + l, < 0 for a pad slot.  Then a group is ANY r rows.  Which rows share a wave decides where the
+//                         waves are in the table at the same edge index: groups of consecutive rows differ by +-4 % in edges,
+//                         which is more of the table than an XCD's L2 holds; cogdl_amd/sweepplan.py: deal_by_degree gives
+//                         every wave the same number of edges and the same mean place in the table (measured on the
+//                         benchmark's graph: L2 hit rate 0.345 -> 0.506, the backward launch 134 -> 105 us;
+//                         profiles/sweep_groups.txt).  The map is read where a group's rows are stored, never per edge.
 // The states of a group stay on the chip for the whole walk: registers for 32 rows (2 VGPRs per row at F = 128 fp32), LDS for 16.
 //
 // The gather ring (sweep_walk).  A wave keeps kSweepRing gathers in flight at every moment of a group's walk: a prologue
@@ -75,6 +82,8 @@ struct SweepArgs {
     int r;          // rows per group (<= kSweepRows)
     uint32_t row_bytes;
     uint32_t table_bytes;  // the gathered table's size, for the descriptor's range check (0 for a table of 2^32 bytes: sweep_args)
+    const int32_t *rows;   // [n_groups * r] the output row of local row l of group g at g * r + l (< 0: a pad slot, never
+                           // written), or NULL: row g * r + l.  Read only where a group's rows are stored (MAPPED).
 };
 
 typedef float SweepF32x32 __attribute__((ext_vector_type(32)));
@@ -184,7 +193,9 @@ __device__ __forceinline__ void sweep_words_turn(uint32_t &p, float &w, uint32_t
 // One wave per row group, four waves per workgroup; groups beyond one round of the grid are walked by the same waves,
 // grid-stride (correct, only less local).  Rows of 128 fp32 columns: one float2 per lane.
 // (The body of both kernels below: the unguarded one is this and nothing else.)
-template <bool WEIGHTED, bool WIDE>
+// MAPPED: the group's rows are named by a.rows (any rows of the structure, dealt to the groups by the layout's builder) instead of
+// being consecutive; only the stores at the group's end differ.
+template <bool WEIGHTED, bool WIDE, bool MAPPED>
 __device__ __forceinline__ void sweep_walk(const SweepArgs &a) {
     constexpr int UNROLL = kSweepUnroll;
     static_assert(UNROLL % kSweepRing == 0 && kWave % UNROLL == 0, "a slot is an edge's place in its batch, a batch never straddles the words at hand");
@@ -262,40 +273,75 @@ __device__ __forceinline__ void sweep_walk(const SweepArgs &a) {
             if (e < end) batch(std::true_type{});
             sweep_drain(v, ncp, ncw);
         }
-        // (rows of a partial last group that do not exist are never stored)
-        const int64_t row0 = g * a.r;
-        const int n_rows = __builtin_amdgcn_readfirstlane((int)min((int64_t)a.r, a.m - row0));
-        char *dst = reinterpret_cast<char *>(a.out) + (uint64_t)row0 * (uint64_t)a.row_bytes + lane_off;
+        if constexpr (MAPPED) {
+            // (the map is read-only for the launch and its index is wave-uniform: scalar loads; every group has a.r slots)
+            const ConstI32 rows = (ConstI32)(uintptr_t)a.rows + g * a.r;
+            char *const dst = reinterpret_cast<char *>(a.out) + lane_off;
 #pragma unroll
-        for (int c = 0; c < kSweepRows; ++c) {
-            if (c < n_rows) {
-                const float2 o = c < kSweepRegRows ? make_float2(lo0[c & 31], lo1[c & 31]) : hi[(c & 15) * kWave];
-                *reinterpret_cast<float2 *>(dst + (uint64_t)c * (uint64_t)a.row_bytes) = o;
+            for (int c = 0; c < kSweepRows; ++c) {
+                if (c < a.r) {
+                    const int row = rows[c];
+                    if (row >= 0) {
+                        const float2 o = c < kSweepRegRows ? make_float2(lo0[c & 31], lo1[c & 31]) : hi[(c & 15) * kWave];
+                        *reinterpret_cast<float2 *>(dst + (uint64_t)row * (uint64_t)a.row_bytes) = o;
+                    }
+                }
+            }
+        } else {
+            // (rows of a partial last group that do not exist are never stored)
+            const int64_t row0 = g * a.r;
+            const int n_rows = __builtin_amdgcn_readfirstlane((int)min((int64_t)a.r, a.m - row0));
+            char *dst = reinterpret_cast<char *>(a.out) + (uint64_t)row0 * (uint64_t)a.row_bytes + lane_off;
+#pragma unroll
+            for (int c = 0; c < kSweepRows; ++c) {
+                if (c < n_rows) {
+                    const float2 o = c < kSweepRegRows ? make_float2(lo0[c & 31], lo1[c & 31]) : hi[(c & 15) * kWave];
+                    *reinterpret_cast<float2 *>(dst + (uint64_t)c * (uint64_t)a.row_bytes) = o;
+                }
             }
         }
     }
 }
 
-template <bool WEIGHTED, bool WIDE>
+template <bool WEIGHTED, bool WIDE, bool MAPPED>
 __global__ __launch_bounds__(256, 4) void rowreduce_sweep_kernel(const SweepArgs a) {
-    sweep_walk<WEIGHTED, WIDE>(a);
+    sweep_walk<WEIGHTED, WIDE, MAPPED>(a);
 }
 
 // The same walk, taken only if the guard says so (see the header comment); a wave that stands down has written nothing.
-template <bool WEIGHTED, bool WIDE>
+template <bool WEIGHTED, bool WIDE, bool MAPPED>
 __global__ __launch_bounds__(256, 4) void rowreduce_sweep_guarded_kernel(const SweepArgs a, const HashGuard guard) {
     if (!guard_runs(guard)) return;
-    sweep_walk<WEIGHTED, WIDE>(a);
+    sweep_walk<WEIGHTED, WIDE, MAPPED>(a);
 }
 
 // The arguments of either kernel for a table of n_src rows; -> WIDE, whether the table's end is beyond a descriptor's reach.
 inline bool sweep_args(SweepArgs &a, const int32_t *goff, const int32_t *src, const void *w, const void *x, void *out, int64_t m,
-                       int64_t n_src, int64_t n_groups, int r, int64_t k) {
+                       int64_t n_src, int64_t n_groups, int r, int64_t k, const int32_t *rows) {
     const uint64_t bytes = (uint64_t)n_src * (uint64_t)k * sizeof(float);
     const bool wide = bytes > 0xffffffffull;
     a = SweepArgs{goff, (const uint32_t *)src, (const float *)w, (const float *)x, (float *)out, m, n_groups, r,
-                  (uint32_t)(k * sizeof(float)), wide ? 0u : (uint32_t)bytes};
+                  (uint32_t)(k * sizeof(float)), wide ? 0u : (uint32_t)bytes, rows};
     return wide;
+}
+
+// Launch the kernel that the arguments ask for: weighted or not, the wide request or the descriptor's, mapped rows or consecutive
+// ones; guarded if `guard` is given.
+template <bool WEIGHTED, bool WIDE, bool MAPPED>
+inline void sweep_launch_as(const SweepArgs &a, const HashGuard *guard, unsigned blocks, hipStream_t s) {
+    if (guard) hipLaunchKernelGGL((rowreduce_sweep_guarded_kernel<WEIGHTED, WIDE, MAPPED>), dim3(blocks), dim3(256), 0, s, a, *guard);
+    else hipLaunchKernelGGL((rowreduce_sweep_kernel<WEIGHTED, WIDE, MAPPED>), dim3(blocks), dim3(256), 0, s, a);
+}
+template <bool WEIGHTED, bool WIDE>
+inline void sweep_launch_rows(const SweepArgs &a, const HashGuard *guard, unsigned blocks, hipStream_t s) {
+    if (a.rows) sweep_launch_as<WEIGHTED, WIDE, true>(a, guard, blocks, s);
+    else sweep_launch_as<WEIGHTED, WIDE, false>(a, guard, blocks, s);
+}
+inline void sweep_launch(const SweepArgs &a, bool wide, const HashGuard *guard, unsigned blocks, hipStream_t s) {
+    if (a.w && !wide) sweep_launch_rows<true, false>(a, guard, blocks, s);
+    else if (a.w) sweep_launch_rows<true, true>(a, guard, blocks, s);
+    else if (!wide) sweep_launch_rows<false, false>(a, guard, blocks, s);
+    else sweep_launch_rows<false, true>(a, guard, blocks, s);
 }
 
 // Waves of one round on the current device (CU count x waves that fit), capped by tuning key 18 (tests: rows per round).

@@ -216,12 +216,13 @@ extern "C" int64_t cogdl_hip_csr_spmm_sweep_round_rows(int64_t k, int dtype) {
     return sweep_round_waves() * kSweepRows;
 }
 
-extern "C" int cogdl_hip_csr_spmm_sweep(const int32_t *goff, const int32_t *src, const void *w, const void *x, void *out,
-                                        int64_t m, int64_t n_src, int64_t n_groups, int r, int64_t k, int64_t nnz, int dtype, void *stream) {
-    if (m < 0 || n_groups < 0 || nnz < 0 || r < 1 || r > kSweepRows) return COGDL_HIP_EINVAL;
-    if (dtype != COGDL_HIP_F32 || k != 2 * kWave) return COGDL_HIP_EUNSUPPORTED;
+// Both sweep entries, with or without a row map and a guard.  rows: n_map = n_groups * r entries (any number of groups that
+// holds the m rows), or NULL for groups of r consecutive rows.
+static int sweep_entry(const int32_t *goff, const int32_t *src, const void *w, const void *x, void *out, int64_t m, int64_t n_src,
+                       int64_t n_groups, int r, int64_t k, int64_t nnz, int dtype, const int32_t *rows, int64_t n_map,
+                       const HashGuard *guard, void *stream) {
     if (m == 0) return COGDL_HIP_OK;
-    if (n_groups != (m + r - 1) / r) return COGDL_HIP_EINVAL;
+    if (rows ? (n_map != n_groups * r || n_map < m) : (n_groups != (m + r - 1) / r)) return COGDL_HIP_EINVAL;
     if (!goff || !x || !out || (nnz > 0 && !src)) return COGDL_HIP_EINVAL;
     if (nnz > COGDL_HIP_SEGMENT_MAX_EDGES) return COGDL_HIP_ERANGE;
     if (!aligned_to(x, sizeof(float2)) || !aligned_to(out, sizeof(float2))) return COGDL_HIP_EALIGN;
@@ -232,13 +233,32 @@ extern "C" int cogdl_hip_csr_spmm_sweep(const int32_t *goff, const int32_t *src,
         return COGDL_HIP_ELAUNCH;
     }
     SweepArgs a;
-    const bool wide = sweep_args(a, goff, src, w, x, out, m, n_src, n_groups, r, k);
+    const bool wide = sweep_args(a, goff, src, w, x, out, m, n_src, n_groups, r, k, rows);
     const unsigned blocks = (unsigned)((std::min(waves, n_groups) + 3) / 4);
-    if (w && !wide) hipLaunchKernelGGL((rowreduce_sweep_kernel<true, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-    else if (w) hipLaunchKernelGGL((rowreduce_sweep_kernel<true, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-    else if (!wide) hipLaunchKernelGGL((rowreduce_sweep_kernel<false, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((rowreduce_sweep_kernel<false, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+    sweep_launch(a, wide, guard, blocks, (hipStream_t)stream);
     return launch_status();
+}
+
+static int sweep_checked(int64_t m, int64_t n_groups, int64_t nnz, int r, int64_t k, int dtype) {
+    if (m < 0 || n_groups < 0 || nnz < 0 || r < 1 || r > kSweepRows) return COGDL_HIP_EINVAL;
+    if (dtype != COGDL_HIP_F32 || k != 2 * kWave) return COGDL_HIP_EUNSUPPORTED;
+    return COGDL_HIP_OK;
+}
+
+extern "C" int cogdl_hip_csr_spmm_sweep(const int32_t *goff, const int32_t *src, const void *w, const void *x, void *out,
+                                        int64_t m, int64_t n_src, int64_t n_groups, int r, int64_t k, int64_t nnz, int dtype, void *stream) {
+    const int rc = sweep_checked(m, n_groups, nnz, r, k, dtype);
+    if (rc != COGDL_HIP_OK) return rc;
+    return sweep_entry(goff, src, w, x, out, m, n_src, n_groups, r, k, nnz, dtype, nullptr, 0, nullptr, stream);
+}
+
+extern "C" int cogdl_hip_csr_spmm_sweep_rows(const int32_t *goff, const int32_t *src, const void *w, const void *x, void *out,
+                                             int64_t m, int64_t n_src, int64_t n_groups, int r, int64_t k, int64_t nnz, int dtype,
+                                             const int32_t *rows, int64_t n_map, void *stream) {
+    const int rc = sweep_checked(m, n_groups, nnz, r, k, dtype);
+    if (rc != COGDL_HIP_OK) return rc;
+    if (!rows && m > 0) return COGDL_HIP_EINVAL;
+    return sweep_entry(goff, src, w, x, out, m, n_src, n_groups, r, k, nnz, dtype, rows, n_map, nullptr, stream);
 }
 
 // ---- guarded launches: the forward pass over a layout cached for a structure seen earlier (rowsweep.h, common.h: HashGuard) ----
@@ -254,30 +274,25 @@ static int make_guard(HashGuard &g, const uint64_t *parts, uint64_t expect, int 
 extern "C" int cogdl_hip_csr_spmm_sweep_guarded(const int32_t *goff, const int32_t *src, const void *w, const void *x, void *out,
                                                 int64_t m, int64_t n_src, int64_t n_groups, int r, int64_t k, int64_t nnz, int dtype,
                                                 const uint64_t *parts, uint64_t expect, int run_if_equal, void *stream) {
-    if (m < 0 || n_groups < 0 || nnz < 0 || r < 1 || r > kSweepRows) return COGDL_HIP_EINVAL;
-    if (dtype != COGDL_HIP_F32 || k != 2 * kWave) return COGDL_HIP_EUNSUPPORTED;
-    HashGuard guard;
-    int rc = make_guard(guard, parts, expect, run_if_equal);
+    int rc = sweep_checked(m, n_groups, nnz, r, k, dtype);
     if (rc != COGDL_HIP_OK) return rc;
-    if (m == 0) return COGDL_HIP_OK;
-    if (n_groups != (m + r - 1) / r) return COGDL_HIP_EINVAL;
-    if (!goff || !x || !out || (nnz > 0 && !src)) return COGDL_HIP_EINVAL;
-    if (nnz > COGDL_HIP_SEGMENT_MAX_EDGES) return COGDL_HIP_ERANGE;
-    if (!aligned_to(x, sizeof(float2)) || !aligned_to(out, sizeof(float2))) return COGDL_HIP_EALIGN;
-    if (n_src <= 0 || n_src > (1 << 23)) return COGDL_HIP_EUNSUPPORTED;  // (24-bit rows, 32-bit byte offsets into x)
-    const int64_t waves = sweep_round_waves();
-    if (waves <= 0) {
-        g_last_hip_error = (int)hipGetLastError();
-        return COGDL_HIP_ELAUNCH;
-    }
-    SweepArgs a;
-    const bool wide = sweep_args(a, goff, src, w, x, out, m, n_src, n_groups, r, k);
-    const unsigned blocks = (unsigned)((std::min(waves, n_groups) + 3) / 4);
-    if (w && !wide) hipLaunchKernelGGL((rowreduce_sweep_guarded_kernel<true, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, guard);
-    else if (w) hipLaunchKernelGGL((rowreduce_sweep_guarded_kernel<true, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, guard);
-    else if (!wide) hipLaunchKernelGGL((rowreduce_sweep_guarded_kernel<false, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, guard);
-    else hipLaunchKernelGGL((rowreduce_sweep_guarded_kernel<false, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, guard);
-    return launch_status();
+    HashGuard guard;
+    rc = make_guard(guard, parts, expect, run_if_equal);
+    if (rc != COGDL_HIP_OK) return rc;
+    return sweep_entry(goff, src, w, x, out, m, n_src, n_groups, r, k, nnz, dtype, nullptr, 0, &guard, stream);
+}
+
+extern "C" int cogdl_hip_csr_spmm_sweep_rows_guarded(const int32_t *goff, const int32_t *src, const void *w, const void *x,
+                                                     void *out, int64_t m, int64_t n_src, int64_t n_groups, int r, int64_t k,
+                                                     int64_t nnz, int dtype, const int32_t *rows, int64_t n_map,
+                                                     const uint64_t *parts, uint64_t expect, int run_if_equal, void *stream) {
+    int rc = sweep_checked(m, n_groups, nnz, r, k, dtype);
+    if (rc != COGDL_HIP_OK) return rc;
+    HashGuard guard;
+    rc = make_guard(guard, parts, expect, run_if_equal);
+    if (rc != COGDL_HIP_OK) return rc;
+    if (!rows && m > 0) return COGDL_HIP_EINVAL;
+    return sweep_entry(goff, src, w, x, out, m, n_src, n_groups, r, k, nnz, dtype, rows, n_map, &guard, stream);
 }
 
 extern "C" int cogdl_hip_csr_spmm_guarded(const int32_t *rowptr, const int32_t *colind, const void *val, const void *x, void *out,

@@ -177,9 +177,15 @@ def csr_spmm_sweep_raw(csc, val, x):
                     else (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
         if pair is not None:
             pair[0].record()
-        rc = _lib.hip().cogdl_hip_csr_spmm_sweep(_lib.ptr(sp.goff), _lib.ptr(sp.src), _lib.ptr(val), _lib.ptr(x), _lib.ptr(out),
-                                                 csc.n_cols, csc.m, sp.n_groups, sp.r, k, sp.nnz, _lib.DTYPE_CODE[x.dtype],
-                                                 _lib.stream_of(x))
+        if sp.rows is None:
+            rc = _lib.hip().cogdl_hip_csr_spmm_sweep(_lib.ptr(sp.goff), _lib.ptr(sp.src), _lib.ptr(val), _lib.ptr(x), _lib.ptr(out),
+                                                     csc.n_cols, csc.m, sp.n_groups, sp.r, k, sp.nnz, _lib.DTYPE_CODE[x.dtype],
+                                                     _lib.stream_of(x))
+        else:
+            rc = _lib.hip().cogdl_hip_csr_spmm_sweep_rows(_lib.ptr(sp.goff), _lib.ptr(sp.src), _lib.ptr(val), _lib.ptr(x),
+                                                          _lib.ptr(out), csc.n_cols, csc.m, sp.n_groups, sp.r, k, sp.nnz,
+                                                          _lib.DTYPE_CODE[x.dtype], _lib.ptr(sp.rows), sp.rows.numel(),
+                                                          _lib.stream_of(x))
         if pair is not None:
             pair[1].record()
             KERNEL_EVENTS.append(pair)
@@ -223,8 +229,13 @@ def csr_spmm_sweep_forward_raw(sp, parts, rowptr, colind, val, x):
         if pair is not None:
             pair[0].record()
         stream = _lib.stream_of(x)
-        rc = lib.cogdl_hip_csr_spmm_sweep_guarded(_lib.ptr(sp.goff), _lib.ptr(sp.src), _lib.ptr(val_p), _lib.ptr(x), _lib.ptr(out), m,
-                                                  sp.n_src, sp.n_groups, sp.r, k, nnz, code, _lib.ptr(parts), sp.hash, 1, stream)
+        if sp.rows is None:
+            rc = lib.cogdl_hip_csr_spmm_sweep_guarded(_lib.ptr(sp.goff), _lib.ptr(sp.src), _lib.ptr(val_p), _lib.ptr(x), _lib.ptr(out), m,
+                                                      sp.n_src, sp.n_groups, sp.r, k, nnz, code, _lib.ptr(parts), sp.hash, 1, stream)
+        else:
+            rc = lib.cogdl_hip_csr_spmm_sweep_rows_guarded(_lib.ptr(sp.goff), _lib.ptr(sp.src), _lib.ptr(val_p), _lib.ptr(x),
+                                                           _lib.ptr(out), m, sp.n_src, sp.n_groups, sp.r, k, nnz, code,
+                                                           _lib.ptr(sp.rows), sp.rows.numel(), _lib.ptr(parts), sp.hash, 1, stream)
         if rc == 0:
             rc = lib.cogdl_hip_csr_spmm_guarded(_lib.ptr(rowptr), _lib.ptr(colind), _lib.ptr(val), _lib.ptr(x), _lib.ptr(out), m, k,
                                                 nnz, code, _lib.ptr(parts), sp.hash, 0, _lib.ptr(ws), ws_bytes, stream)

@@ -200,6 +200,22 @@ COGDL_API int cogdl_hip_csr_spmm_guarded(const int32_t *rowptr, const int32_t *c
                                          uint64_t expect, int run_if_equal, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Sweep over groups of ANY rows (added within ABI v9: new symbols only): the two sweep entries above with a row map.
+ *   rows [n_map]          n_map = n_groups * r: the output row of local row l of group g at g * r + l; a negative entry is a
+ *                         pad slot that is never written.  Every row of out must be named exactly once (a row with no edge is
+ *                         stored as zeros by the group that names it); n_groups is the caller's, with n_groups * r >= m.
+ * The high 8 bits of a src word are the local row l.  The map is read only where a group's rows are stored, never per edge.
+ * Its length is checked here (COGDL_HIP_EINVAL); that every entry is < m is the layout builder's duty
+ * (cogdl_amd/sweepplan.py checks it before anything is enqueued).  Bit-identical to cogdl_hip_csr_spmm as above. */
+COGDL_API int cogdl_hip_csr_spmm_sweep_rows(const int32_t *goff, const int32_t *src, const void *w, const void *x, void *out,
+                                            int64_t m, int64_t n_src, int64_t n_groups, int r, int64_t k, int64_t nnz, int dtype,
+                                            const int32_t *rows, int64_t n_map, void *stream);
+COGDL_API int cogdl_hip_csr_spmm_sweep_rows_guarded(const int32_t *goff, const int32_t *src, const void *w, const void *x,
+                                                    void *out, int64_t m, int64_t n_src, int64_t n_groups, int r, int64_t k,
+                                                    int64_t nnz, int dtype, const int32_t *rows, int64_t n_map,
+                                                    const uint64_t *parts, uint64_t expect, int run_if_equal, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * 64-bit CSR ("big CSR", ABI v7): graphs of 2^31 edges and more -- ogbn-papers100M as CogDL feeds it to GCN
  * (symmetrised + coalesced, cogdl/datasets/ogb.py:50-55: 3.2e9 edges).  The reference cannot represent them: the
  * dispatcher casts row pointers to int32 (utils/spmm_utils.py:106), csr_spmm_cpu walks `int` edge offsets and
