@@ -40,7 +40,8 @@ _finder = None
 
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
             metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False, readout=False,
-            relational=False, genconv=False, disengcn=False, contrast=False, netsmf=False, metapath=False, prone=False):
+            relational=False, genconv=False, disengcn=False, contrast=False, netsmf=False, metapath=False, prone=False,
+            kg_eval=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -146,6 +147,16 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     edge weights are not all equal, a graph with self loops, a graph without edges and step == 1 reach the reference's
     forward; the "sc" filter, any other name and a matrix that is not square with unit entries and an empty diagonal reach the
     reference's propagate.
+    kg_eval=True rebinds TripleModelWrapper.eval_step in cogdl.wrappers.model_wrapper.link_prediction.triple_link_prediction_mw,
+    and `cal_mrr` in cogdl.utils.link_prediction_utils with its by-name copy in
+    cogdl.wrappers.model_wrapper.link_prediction.gnn_kg_link_prediction_mw (opt-in: the loaders are read, not iterated; the rank
+    of a target that ties with other candidates is 1 + greater + equal_before where the reference's is whatever its sort does)
+    to cogdl_amd.kgrank_compat: the filtered evaluation of transe, distmult, complex and rotate and the raw evaluation of compgcn
+    and rgcn are counts from the library's rank_all operator (HIP kernels for CUDA tensors -- dot on the fp32 MFMA, the two
+    distances on the VALU -- the OpenMP host twin otherwise): no [B, N, D] gather, no [B, N] sort, no read-back per triple; the
+    filter lists are built once per dataset with torch sort / unique.  cal_mrr also serves protocol="filtered" when its new
+    optional `seen_triples` argument is given.  Any other model class reaches the reference's eval_step, ConvELayer scoring
+    the reference's cal_mrr.
     linear=True additionally routes torch.nn.functional.linear -- i.e. the unchanged nn.Linear inside every CogDL
     layer -- through cogdl_amd.linear (hand-written MFMA weight gradient for full-graph shapes)."""
     global _finder
@@ -255,6 +266,13 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
             pass
         if not prone_compat.install():
             raise _lib_error("install(prone=True): ProNE.forward / propagate could not be rebound")
+    if kg_eval:
+        from . import kgrank_compat
+
+        for name in (kgrank_compat._UTILS, kgrank_compat._WRAPPER, kgrank_compat._HOLDER) + tuple(m for _, m, _ in kgrank_compat._MODELS):
+            _import_target(name, "kg_eval")  # (before anything is rebound: the holder copies the name it gets back at uninstall())
+        if not kgrank_compat.install():
+            raise _lib_error("install(kg_eval=True): TripleModelWrapper.eval_step / cal_mrr could not be rebound")
     su = sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):

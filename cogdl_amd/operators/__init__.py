@@ -28,6 +28,10 @@
     spectral.py      filter_step, bessel_i, spectral_filter (also exported here)   (cogdl/utils/prone_utils.py:26-176,
                                                                                     ProNE._chebyshev_gaussian, models/emb/prone.py)
 
+    kgrank.py        rank_all, ranks (also exported here)              (TripleModelWrapper.eval_step,
+                                                                        wrappers/model_wrapper/link_prediction/triple_link_prediction_mw.py:84-132;
+                                                                        cal_mrr, cogdl/utils/link_prediction_utils.py:8-28)
+
     ops.py           scatter_add, op_aggr, s_*_e_sum / s_*_e_mean (fused HIP), s_*_e, s_*_t   (cogdl/operators/ops.py)
 
 Submodules are imported lazily: GPU modules load libcogdl_hip.so at import and raise if it
@@ -76,4 +80,8 @@ def __getattr__(name):
         from . import spectral
 
         return getattr(spectral, name)
+    if name in ("rank_all", "ranks"):
+        from . import kgrank
+
+        return getattr(kgrank, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

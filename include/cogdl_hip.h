@@ -1158,6 +1158,41 @@ COGDL_API int cogdl_hip_csr_filter_step(const int32_t *rowptr, const int32_t *co
                               const void *z2, float c2, const float *dst_scale, void *acc, float d, void *workspace,
                               size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * All-entity ranking for knowledge-graph link prediction (added within ABI v9: new symbols only; csrc/kgrank.hip).  For each
+ * of M prepared query rows q[i] (fp32 [M, D]) and its target[i] (int32 [M], in [0, N)): how many rows e of table (fp32
+ * [N, D]) score above the target's row, and how many score equal, without a [M, N] score matrix or a sort:
+ *     counts[i] = (greater, equal_before, equal_after)     int32 [M, 3]
+ *                 over the candidates e != target[i] that filter list i does not name:
+ *                 s(i, e) > s(i, t);   s(i, e) == s(i, t) and e < t;   s(i, e) == s(i, t) and e > t
+ * kind  COGDL_HIP_KG_DOT  s = SUM_k q[k] * table[e, k]                              (fp32 MFMA; gamma is not read)
+ *       COGDL_HIP_KG_L1   s = gamma - SUM_k |q[k] - table[e, k]|                    (VALU)
+ *       COGDL_HIP_KG_CL2  s = gamma - SUM_{k < D/2} |(q[k] - table[e, k]) + i (q[k + D/2] - table[e, k + D/2])|   (VALU; D even)
+ * The order of every float32 operation is csrc/kgrank_law.h's: one pass over k in ascending order per pair of rows, no split
+ * over k, the target's score from the same operations as a candidate's -- so `==` is exact, the counts are integers, and
+ * both are equal from run to run and equal to the host twin's (cogdl_host_kg_rank).  A NaN score is counted nowhere.
+ * filt_ptr int32 [M + 1] (non-decreasing, filt_ptr[0] = 0, filt_ptr[M] = filt_len), filt_idx int32 [filt_len]: per query the
+ * ids to leave out, IN NON-DECREASING ORDER within a query (the pass recognises a duplicate as an entry equal to its
+ * predecessor and counts it once); the target is never left out even if listed.  filt_len == 0: no filter, both may be NULL.
+ * The filter is a correction pass after the count over all N: one score per list entry under the same law.
+ * Ids outside [0, N) (a target: its counts are 0; a list entry: passed over) and a malformed filt_ptr give wrong numbers,
+ * never an access outside the operands.
+ * workspace: cogdl_hip_kg_rank_workspace_bytes(M, N, D, kind) bytes, 4-byte aligned (the targets' scores).  Launches on
+ * `stream`; no allocation, no synchronisation, no host read.  M == 0: success, nothing launched.  Pointers aligned to 4 bytes
+ * (COGDL_HIP_EALIGN otherwise); an unknown kind, odd D with CL2 or a negative size: COGDL_HIP_EINVAL; sizes of 2^31 - 1 and
+ * more: COGDL_HIP_ERANGE.
+ * cogdl_hip_kg_rank_slice_entities: the number of consecutive table rows one workgroup of the counting launch walks for
+ * these sizes (slice s covers rows [s * len, (s + 1) * len)); for tests that place targets on slice boundaries.
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define COGDL_HIP_KG_DOT 0
+#define COGDL_HIP_KG_L1 1
+#define COGDL_HIP_KG_CL2 2
+COGDL_API size_t cogdl_hip_kg_rank_workspace_bytes(int64_t M, int64_t N, int64_t D, int kind);
+COGDL_API int64_t cogdl_hip_kg_rank_slice_entities(int64_t M, int64_t N, int64_t D, int kind);
+COGDL_API int cogdl_hip_kg_rank(const float *q, const float *table, const int32_t *target, int64_t M, int64_t N, int64_t D,
+                      int kind, float gamma, const int32_t *filt_ptr, const int32_t *filt_idx, int64_t filt_len,
+                      int32_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,14 @@ COGDL_HOST_API int cogdl_host_csr_filter_step(const int32_t *rowptr, const int32
                                               const float *z1, float c1, const float *z2, float c2, const float *dst_scale,
                                               float *acc, float d);
 
+/* All-entity ranking counts; the host twin of cogdl_hip_kg_rank (include/cogdl_hip.h, where the contract is spelled out): same
+ * arguments minus workspace and stream, all pointers host memory.  Both sides follow csrc/kgrank_law.h, so for equal inputs
+ * all three counts of every query are EXACTLY the GPU's.  OpenMP over the queries; the result does not depend on the number
+ * of threads. */
+COGDL_HOST_API int cogdl_host_kg_rank(const float *q, const float *table, const int32_t *target, int64_t M, int64_t N,
+                                      int64_t D, int kind, float gamma, const int32_t *filt_ptr, const int32_t *filt_idx,
+                                      int64_t filt_len, int32_t *counts);
+
 #ifdef __cplusplus
 }
 #endif
