@@ -180,6 +180,10 @@ HIP_SIGNATURES = {
     "cogdl_hip_kg_rank_workspace_bytes": ([_i64, _i64, _i64, _i32], _sz),
     "cogdl_hip_kg_rank_slice_entities": ([_i64, _i64, _i64, _i32], _i64),
     "cogdl_hip_kg_rank": ([_vp, _vp, _vp, _i64, _i64, _i64, _i32, _f32, _vp, _vp, _i64, _vp, _vp, _sz, _vp], _i32),
+    # sampled triple scoring (csrc/kgscore.hip)
+    "cogdl_hip_kg_score": ([_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _vp, _vp], _i32),
+    "cogdl_hip_kg_score_grad_q": ([_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp], _i32),
+    "cogdl_hip_kg_score_grad_table": ([_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp], _i32),
 }
 
 MAX_SEGMENTS = 64  # COGDL_HIP_MAX_SEGMENTS
@@ -216,6 +220,9 @@ HOST_SIGNATURES = {
     "cogdl_host_sort_pool_bwd": ([_vp, _vp, _i64, _i64, _i64, _i64, _vp], _i32),
     "cogdl_host_csr_filter_step": ([_vp] * 5 + [_i64, _i64, _i64, _i32, _f32, _f32, _vp, _f32, _vp, _f32, _vp, _vp, _f32], _i32),
     "cogdl_host_kg_rank": ([_vp, _vp, _vp, _i64, _i64, _i64, _i32, _f32, _vp, _vp, _i64, _vp], _i32),
+    "cogdl_host_kg_score": ([_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _vp], _i32),
+    "cogdl_host_kg_score_grad_q": ([_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp], _i32),
+    "cogdl_host_kg_score_grad_table": ([_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp], _i32),
 }
 
 EUNSUPPORTED = 7  # COGDL_HIP_EUNSUPPORTED

@@ -5,6 +5,9 @@
 // order of float32 operations over k; it does not depend on the tile, the workgroup or the launch that computes it, there is
 // no split over k, and the target's score comes from the same operations as every candidate's.  That is what makes `==`
 // between two scores meaningful.  Both libraries are built with -ffp-contract=off: an fma happens where fmaf is written.
+// (kgscore_law.h, the law of sampled scoring for training, reuses the per-term steps below but sums them in another order --
+// 64 slot partials and a butterfly, which a wave can execute; here one thread owns a pair of rows and walks k sequentially.
+// The difference is intended: the two operators never compare scores with each other.)
 //
 //   dot   acc = +0;  for k = 0 .. D-1:    acc = fmaf(q[k], t[k], acc);                                           s = acc
 //         (bit for bit what v_mfma_f32_32x32x2_f32 computes from a zero accumulator with k ascending; fmaf(q, t, .) and

@@ -41,7 +41,7 @@ _finder = None
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
             metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False, readout=False,
             relational=False, genconv=False, disengcn=False, contrast=False, netsmf=False, metapath=False, prone=False,
-            kg_eval=False):
+            kg_eval=False, kg_train=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -157,6 +157,15 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     filter lists are built once per dataset with torch sort / unique.  cal_mrr also serves protocol="filtered" when its new
     optional `seen_triples` argument is given.  Any other model class reaches the reference's eval_step, ConvELayer scoring
     the reference's cal_mrr.
+    kg_train=True rebinds KGEModel.forward in cogdl.models.emb.knowledge_base (opt-in: no longer the unchanged model, and the sums
+    over the embedding width are re-associated -- float32 rounding apart, the same numbers) to cogdl_amd.kgtrain_compat: the two
+    forward calls of TripleModelWrapper.train_step for transe, distmult, complex and rotate -- the negative scores [B, K] of a
+    head-batch or tail-batch and the positive scores [B, 1] -- are the [B, D] query of cogdl_amd.kgrank.prepare_query in torch
+    and one call of the library's sampled_scores operator against the entity table (HIP kernels for CUDA tensors, the OpenMP
+    host twin otherwise): no [B, K, D] gather, no elementwise kernels of that size kept for backward, and the gradient of the
+    entity table is a sum in a fixed order instead of an atomic scatter, equal from run to run.  The loss, the self-adversarial
+    softmax and the regulariser stay the reference's.  Any other model class, a subclass with its own `score` and an unknown
+    mode reach the reference's forward.  Not for use under torch.cuda.graph capture.
     linear=True additionally routes torch.nn.functional.linear -- i.e. the unchanged nn.Linear inside every CogDL
     layer -- through cogdl_amd.linear (hand-written MFMA weight gradient for full-graph shapes)."""
     global _finder
@@ -273,6 +282,13 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
             _import_target(name, "kg_eval")  # (before anything is rebound: the holder copies the name it gets back at uninstall())
         if not kgrank_compat.install():
             raise _lib_error("install(kg_eval=True): TripleModelWrapper.eval_step / cal_mrr could not be rebound")
+    if kg_train:
+        from . import kgtrain_compat
+
+        for name in (kgtrain_compat._MODULE,) + tuple(m for _, m, _ in kgtrain_compat._MODELS):
+            _import_target(name, "kg_train")
+        if not kgtrain_compat.install():
+            raise _lib_error("install(kg_train=True): KGEModel.forward could not be rebound")
     su = sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):

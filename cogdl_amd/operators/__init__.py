@@ -32,6 +32,8 @@
                                                                         wrappers/model_wrapper/link_prediction/triple_link_prediction_mw.py:84-132;
                                                                         cal_mrr, cogdl/utils/link_prediction_utils.py:8-28)
 
+    kgscore.py       sampled_scores (also exported here)               (KGEModel.forward, models/emb/knowledge_base.py:52-101)
+
     ops.py           scatter_add, op_aggr, s_*_e_sum / s_*_e_mean (fused HIP), s_*_e, s_*_t   (cogdl/operators/ops.py)
 
 Submodules are imported lazily: GPU modules load libcogdl_hip.so at import and raise if it
@@ -84,4 +86,8 @@ def __getattr__(name):
         from . import kgrank
 
         return getattr(kgrank, name)
+    if name == "sampled_scores":
+        from . import kgscore
+
+        return kgscore.sampled_scores
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -1193,6 +1193,36 @@ COGDL_API int cogdl_hip_kg_rank(const float *q, const float *table, const int32_
                       int kind, float gamma, const int32_t *filt_ptr, const int32_t *filt_idx, int64_t filt_len,
                       int32_t *counts, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Sampled triple scoring for knowledge-graph embedding training (added within ABI v9: new symbols only; csrc/kgscore.hip).
+ * For each of B prepared query rows q[b] (fp32 [B, D]) and the K table rows idx[b, :] names (int32 [B, K]; table fp32 [N, D]):
+ *     scores[b, j] = s(q[b], table[idx[b, j]])                                  fp32 [B, K]      cogdl_hip_kg_score
+ *     grad_q[b, k] = SUM_j g[b, j] * ds/dq_k                                    fp32 [B, D]      cogdl_hip_kg_score_grad_q
+ *     grad_table[e, k] = SUM_{(b, j): idx[b, j] == e} g[b, j] * ds/dt_k         fp32 [N, D]      cogdl_hip_kg_score_grad_table
+ * with kind and gamma as for cogdl_hip_kg_rank (COGDL_HIP_KG_DOT / _L1 / _CL2).  Nothing of size [B, K, D] exists.  The order
+ * of every float32 operation is csrc/kgscore_law.h's (a score is a pure function of its two rows: 64 slot partials and a
+ * fixed butterfly -- not kg_rank's sequential order, the two never compare scores); there are no float atomics, so all three
+ * results are equal from run to run and equal, bit for bit, to the host twins' (cogdl_host_kg_score*).
+ * g fp32 [B, K] is the gradient that arrives for scores.  occ_ptr int32 [N + 1], occ_pos int32 [B K]: the inverted index of
+ * idx -- occ_pos[occ_ptr[e] .. occ_ptr[e + 1]) are the flat positions b K + j at which e occurs, ascending; ids outside
+ * [0, N) are in no list (occ_ptr[0] need not be 0).  grad_table writes EVERY row, zeros included: no memset precedes it.
+ * An idx entry outside [0, N) scores NaN and contributes to no gradient; malformed idx / occ_ptr / occ_pos give wrong numbers,
+ * never an access outside the operands.
+ * Launches on `stream`; no workspace, no allocation, no synchronisation, no host read.  Checked in this order by all three:
+ * an unknown kind, odd D with CL2 or a negative size: COGDL_HIP_EINVAL, sizes (B K included) of 2^31 - 1 and more:
+ * COGDL_HIP_ERANGE; an empty output (score: B or K of 0; grad_q: B or D of 0; grad_table: N or D of 0): success, nothing
+ * launched; a NULL pointer to a non-empty operand: COGDL_HIP_EINVAL; pointers aligned to 4 bytes (COGDL_HIP_EALIGN otherwise;
+ * 16-byte loads are used where base addresses and D allow, the bits are the same either way); D above 16384:
+ * COGDL_HIP_ERANGE.  Not for use under stream capture.
+ * ------------------------------------------------------------------------------------------------------------------- */
+COGDL_API int cogdl_hip_kg_score(const float *q, const float *table, const int32_t *idx, int64_t B, int64_t K, int64_t N,
+                       int64_t D, int kind, float gamma, float *scores, void *stream);
+COGDL_API int cogdl_hip_kg_score_grad_q(const float *q, const float *table, const int32_t *idx, const float *g, int64_t B,
+                       int64_t K, int64_t N, int64_t D, int kind, float *grad_q, void *stream);
+COGDL_API int cogdl_hip_kg_score_grad_table(const float *q, const float *table, const float *g, const int32_t *occ_ptr,
+                       const int32_t *occ_pos, int64_t B, int64_t K, int64_t N, int64_t D, int kind, float *grad_table,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -194,6 +194,19 @@ COGDL_HOST_API int cogdl_host_kg_rank(const float *q, const float *table, const 
                                       int64_t D, int kind, float gamma, const int32_t *filt_ptr, const int32_t *filt_idx,
                                       int64_t filt_len, int32_t *counts);
 
+/* Sampled triple scores and their two gradients; the host twins of cogdl_hip_kg_score, cogdl_hip_kg_score_grad_q and
+ * cogdl_hip_kg_score_grad_table (include/cogdl_hip.h, where the contract is spelled out): same arguments minus the stream, all
+ * pointers host memory, no alignment requirement, no limit on D.  Both sides follow csrc/kgscore_law.h, so for equal inputs
+ * scores and both gradients are EXACTLY the GPU's.  OpenMP over the query rows (the entities for grad_table); the result does
+ * not depend on the number of threads. */
+COGDL_HOST_API int cogdl_host_kg_score(const float *q, const float *table, const int32_t *idx, int64_t B, int64_t K, int64_t N,
+                                       int64_t D, int kind, float gamma, float *scores);
+COGDL_HOST_API int cogdl_host_kg_score_grad_q(const float *q, const float *table, const int32_t *idx, const float *g, int64_t B,
+                                              int64_t K, int64_t N, int64_t D, int kind, float *grad_q);
+COGDL_HOST_API int cogdl_host_kg_score_grad_table(const float *q, const float *table, const float *g, const int32_t *occ_ptr,
+                                                  const int32_t *occ_pos, int64_t B, int64_t K, int64_t N, int64_t D, int kind,
+                                                  float *grad_table);
+
 #ifdef __cplusplus
 }
 #endif
