@@ -15,6 +15,13 @@
 // blocks; the LEADING workgroups of the same launch treat them chunk-parallel (rowreduce.h bookkeeping), for any H:
 // per-piece statistics ((max, sum) forward, <softmax, grad> backward) by a whole workgroup; a second kernel merges a
 // row's piece records in chunk order (each piece workgroup redoes that tiny merge itself) and writes the piece.
+//
+// Non-finite logits: per (row, head) the result is torch.softmax's.  A -inf logit next to a finite one gives exactly 0 (the
+// usual attention mask; masked_fill(-1e9) IS -inf once the logits are float16); a run of nothing but -inf, or with a +inf or
+// a NaN in it, is NaN; nothing leaves its (row, head).  A lane, a batch or a piece that has seen nothing but -inf is an empty
+// partial (max -inf, sum 0): the statistics subtract 0 instead of a -inf maximum, once per batch, so that what is summed is
+// exp(-inf - 0) = 0 and not exp(-inf - -inf) = NaN; the NaN of a dead run comes out of the final exp(v - max) / sum by
+// itself.  The backward needs nothing: s (g - sum s g) is 0 for s = 0 and NaN for a NaN run.
 #include "rowreduce.h"
 
 #include <type_traits>
@@ -70,7 +77,10 @@ constexpr int kEsUnroll = 4;
 template <typename T>
 __device__ __forceinline__ MaxSum maxsum_strided(const T *__restrict__ a, int64_t i0, int64_t end, int64_t stride) {
     if (i0 + stride >= end) {  // at most one element for this lane (short rows: the common case on small graphs)
-        if (i0 < end) return {to_f32<T>(a[i0]), 1.f};
+        if (i0 < end) {
+            const float v = to_f32<T>(a[i0]);
+            return {v, (v == -INFINITY) ? 0.f : 1.f};  // a masked element is an empty partial (exp(-inf - -inf) otherwise)
+        }
         return {-INFINITY, 0.f};
     }
     MaxSum acc{-INFINITY, 0.f};
@@ -85,9 +95,10 @@ __device__ __forceinline__ MaxSum maxsum_strided(const T *__restrict__ a, int64_
 #pragma unroll
         for (int u = 1; u < kEsUnroll; ++u) bm = fmaxf(bm, v[u]);
         const float mn = fmaxf(acc.m, bm);
+        const float ms = (mn == -INFINITY) ? 0.f : mn;  // nothing but -inf so far: exp(-inf - 0) == 0, not exp(-inf - -inf)
         float ssum = 0.f;
 #pragma unroll
-        for (int u = 0; u < kEsUnroll; ++u) ssum += es_exp(v[u] - mn);  // masked slots: exp(-inf) == 0
+        for (int u = 0; u < kEsUnroll; ++u) ssum += es_exp(v[u] - ms);  // masked slots: exp(-inf) == 0
         acc.s = ((acc.s == 0.f) ? 0.f : acc.s * es_exp(acc.m - mn)) + ssum;
         acc.m = mn;
     }
@@ -164,7 +175,7 @@ __device__ __forceinline__ MaxSum4 maxsum_strided4(const float *__restrict__ a, 
         if (i0 < end) {
             get4(ld4(a + i0), acc.m);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) acc.s[c] = 1.f;
+            for (int c = 0; c < 4; ++c) acc.s[c] = (acc.m[c] == -INFINITY) ? 0.f : 1.f;  // (masked: an empty partial)
         }
         return acc;
     }
@@ -184,9 +195,10 @@ __device__ __forceinline__ MaxSum4 maxsum_strided4(const float *__restrict__ a, 
 #pragma unroll
             for (int u = 1; u < kEsUnroll; ++u) bm = fmaxf(bm, v[u][c]);
             const float mn = fmaxf(acc.m[c], bm);
+            const float ms = (mn == -INFINITY) ? 0.f : mn;  // (as in maxsum_strided)
             float ssum = 0.f;
 #pragma unroll
-            for (int u = 0; u < kEsUnroll; ++u) ssum += es_exp(v[u][c] - mn);
+            for (int u = 0; u < kEsUnroll; ++u) ssum += es_exp(v[u][c] - ms);
             acc.s[c] = ((acc.s[c] == 0.f) ? 0.f : acc.s[c] * es_exp(acc.m[c] - mn)) + ssum;
             acc.m[c] = mn;
         }

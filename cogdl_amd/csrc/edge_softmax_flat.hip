@@ -99,11 +99,22 @@ __device__ __forceinline__ float2 ld_rec(const float2 *p) {
     return make_float2(__uint_as_float((unsigned)bits), __uint_as_float((unsigned)(bits >> 32)));
 }
 
+// Non-finite operands.  The contract is torch.softmax's per (row, head): a -inf logit next to a finite one gives exactly
+// 0, a run of nothing but -inf (or with a +inf or a NaN in it) gives NaN, and nothing leaves its (row, head).  A piece of
+// a row whose logits are all -inf is an EMPTY partial (max -inf, sum 0): every statistic below subtracts 0 instead of a
+// -inf maximum, so that exp(-inf - 0) = 0 is summed and not exp(-inf - -inf) = NaN.  The NaN of a dead run comes out of
+// the final exp(v - max_row) / sum_row on its own.
+__device__ __forceinline__ float finite_max(float mx) { return (mx == -INFINITY) ? 0.f : mx; }
+// A published record must not have .y == 0 (that is "not yet published"): an empty partial is published with this sum.
+constexpr float kMaskedSum = -1.f;
+
 // (max, sum) pairs: b's elements follow a's.
 __device__ __forceinline__ float2 ms_combine(float2 a, float2 b) {
+    // An empty partial has .y == 0 in registers and kMaskedSum in a published record (publish(), below): both are
+    // `<= 0`, a NaN sum is not and goes through.
     const float mx = fmaxf(a.x, b.x);
-    const float sa = (a.y == 0.f) ? 0.f : a.y * es_exp(a.x - mx);
-    const float sb = (b.y == 0.f) ? 0.f : b.y * es_exp(b.x - mx);
+    const float sa = (a.y <= 0.f) ? 0.f : a.y * es_exp(a.x - mx);
+    const float sb = (b.y <= 0.f) ? 0.f : b.y * es_exp(b.x - mx);
     return make_float2(mx, sa + sb);
 }
 
@@ -159,8 +170,9 @@ __device__ __forceinline__ float2 wg_piece_lds(const S *tile, const S *tile_g, i
         float mx = -INFINITY;
         for (int i = t; i < cnt; i += kThreads) mx = fmaxf(mx, lds_ld(tile, off + i));
         mx = wg_head_reduce<true>(mx, h, red);
+        const float ms = finite_max(mx);
         float sum = 0.f;
-        for (int i = t; i < cnt; i += kThreads) sum += es_exp(lds_ld(tile, off + i) - mx);
+        for (int i = t; i < cnt; i += kThreads) sum += es_exp(lds_ld(tile, off + i) - ms);
         return make_float2(mx, wg_head_reduce<false>(sum, h, red));
     }
 }
@@ -200,9 +212,10 @@ __device__ __forceinline__ float2 wg_piece_global(const T *__restrict__ a, const
 #pragma unroll
             for (int u = 1; u < U; ++u) bm = fmaxf(bm, v[u]);
             const float mn = fmaxf(mx, bm);
+            const float ms = finite_max(mn);
             float s = 0.f;
 #pragma unroll
-            for (int u = 0; u < U; ++u) s += es_exp(v[u] - mn);
+            for (int u = 0; u < U; ++u) s += es_exp(v[u] - ms);
             sum = ((sum == 0.f) ? 0.f : sum * es_exp(mx - mn)) + s;
             mx = mn;
         }
@@ -214,13 +227,15 @@ __device__ __forceinline__ float2 wg_piece_global(const T *__restrict__ a, const
 
 // Publish the record of (tile, slot): threads 0..h-1 store their head's pair as ONE aligned 8-byte write-through
 // store.  The record is its own flag ("granule", MI355X_MICROARCH.md recipe R2): the init kernel zeroes every record
-// and a published one never has .y == 0 (forward: .y = sum of exp(v - max) >= 1; backward: .y = 1), so a reader that
+// and a published one never has .y == 0 (forward: .y = sum of exp(v - max) >= 1, NaN, or kMaskedSum for a piece of
+// nothing but -inf, whose sum is 0; backward: .y = 1), so a reader that
 // sees .y != 0 sees the whole record -- no drain of the store queue, no separate flag, no counter.
 __device__ __forceinline__ int slot_of(int64_t start, int64_t c, int tile_e) { return start <= c * tile_e ? 0 : 1; }
 template <bool BWD>
 __device__ __forceinline__ void publish(const Params &p, int64_t tile, int slot, float2 mine) {
     if (p.debug & 1) return;
-    if ((int)threadIdx.x < p.h) st_rec(p.rec + (tile * 2 + slot) * p.h + threadIdx.x, mine.x, BWD ? 1.f : mine.y);
+    if ((int)threadIdx.x < p.h)
+        st_rec(p.rec + (tile * 2 + slot) * p.h + threadIdx.x, mine.x, BWD ? 1.f : (mine.y == 0.f ? kMaskedSum : mine.y));
 }
 
 // (slot_of: record slot of a row in tile c -- the row is known to intersect c and to extend beyond it.)
@@ -375,12 +390,13 @@ __device__ __forceinline__ float2 wg_piece_lds2(const S *tile, const S *tile_g, 
         }
         m0 = wg_head_reduce<true>(m0, hp, red);
         m1 = wg_head_reduce<true>(m1, hp, red);
+        const float ms0 = finite_max(m0), ms1 = finite_max(m1);
         float s0 = 0.f, s1 = 0.f;
         for (int i = t; i < nw; i += kThreads) {
             float a0, a1;
             lds_ld2(tile, w0 + i, a0, a1);
-            s0 += es_exp(a0 - m0);
-            s1 += es_exp(a1 - m1);
+            s0 += es_exp(a0 - ms0);
+            s1 += es_exp(a1 - ms1);
         }
         r0 = m0;
         r1 = m1;
@@ -653,6 +669,10 @@ __global__ __launch_bounds__(kThreads, WPE) void es_flat_kernel(const Params p) 
             }
             wg_slot_reduce<V, true>(mxs, h, red);
             mark(1);  // maximum pass + workgroup reduction
+            // a tile of nothing but -inf: subtract 0 (in place: no register for a second copy; the sum then comes out
+            // as exactly 0, which is how the true maximum is put back when the statistics are handed over below)
+#pragma unroll
+            for (int k = 0; k < V; ++k) mxs[k] = finite_max(mxs[k]);
 #pragma unroll
             for (int k = 0; k < V; ++k) x[k] = 0.f;
 #pragma unroll
@@ -672,7 +692,7 @@ __global__ __launch_bounds__(kThreads, WPE) void es_flat_kernel(const Params p) 
             if (t * V < h || (h < V && t == 0)) {
 #pragma unroll
                 for (int k = 0; k < V; ++k)
-                    if (t * V + k < h) pstat[t * V + k] = make_float2(mxs[k], x[k]);
+                    if (t * V + k < h) pstat[t * V + k] = make_float2(x[k] == 0.f ? -INFINITY : mxs[k], x[k]);
             }
         }
         __syncthreads();

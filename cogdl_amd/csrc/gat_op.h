@@ -40,10 +40,22 @@ __device__ __forceinline__ float leaky(float v, float slope) { return v > 0.f ? 
 // Backward: a[e,h] = exp(s - max) / sum as ONE fused multiply-add and ONE v_exp: exp2(s * log2(e) + nml) with
 // nml = -(max * log2(e) + log2(sum)) per (row, head) -- where subtract / scale / v_exp / multiply by 1 / sum were four.  The
 // argument carries one rounding instead of two plus the reciprocal's (a moves by ~1e-7 relative; parity of the backward is a
-// tolerance).  A row that has edges has sum >= 1 (its maximum contributes exp(0)); sum == 0 gives nml = -inf, a = 0.
+// tolerance).  A row that has edges has sum >= 1 (its maximum contributes exp(0)) unless the run is dead (below): then
+// nml is +inf or NaN and every a of the run is NaN, as autograd of the softmax gives.  (An empty row's nml is never read.)
 constexpr float kLog2e = 1.4426950408889634f;
 __device__ __forceinline__ float gat_neg_max_log(float mx, float ls) {
-    return ls > 0.f ? -(mx * kLog2e + __log2f(ls)) : -INFINITY;
+    return (mx == INFINITY) ? NAN : -(mx * kLog2e + __log2f(ls));
+}
+// Non-finite scores.  The contract per (row, head) is torch.softmax's: an edge whose score is -inf (attn_col[u] = -inf: a
+// masked source) weighs exactly 0 next to a finite one; a run of nothing but -inf scores, or with a +inf or a NaN in it, is
+// NaN in out and in every gradient that autograd makes NaN; an empty row stays 0.  The running maximum tells the three
+// apart: -inf = no edge seen, -FLT_MAX = edges seen and every score -inf so far (set once per chunk by gat_seen_edges, so
+// that the per-edge code never forms -inf - -inf), +inf = a +inf score.
+__device__ __forceinline__ float gat_seen_edges(float mx) { return fmaxf(mx, -3.402823466e+38f); }
+// what the accumulator of a finished (row, head) is multiplied by
+__device__ __forceinline__ float gat_row_scale(float mx, float lsum) {
+    if (lsum > 0.f && mx < INFINITY) return 1.f / lsum;
+    return (mx == -INFINITY) ? 0.f : NAN;  // empty row -> zeros; dead run, +inf or NaN score -> NaN
 }
 __device__ __forceinline__ float gat_softmax_weight(float s, float nml) {
     return __builtin_amdgcn_exp2f(__builtin_fmaf(s, kLog2e, nml));
@@ -254,8 +266,9 @@ struct GatFwdOp {
             if constexpr (ACH > 0) ac_u = chunk_scalars_row<ACH, LPR>(c.cs, jpos)[ACH == 1 ? 0 : c.hd];
             else ac_u = b.ac[u];
             // Online softmax with ONE exponential per (edge, lane): of exp(mx - mn) and exp(sc - mn), mn = max(mx, sc), one
-            // is exp(0) = 1 and the other t = exp(-|sc - mx|) (mx = -inf at the start of a row: t = 0 = the rescale of
-            // the empty state).  Round 6: these kernels are bound by instruction issue on hub-heavy graphs (SQ counters,
+            // is exp(0) = 1 and the other t = exp(-|sc - mx|) (mx = -FLT_MAX at the start of a row, chunk_begin: t = 0 = the
+            // rescale of the empty state for a finite first score, and p = 0 for a -inf one).  Round 6: these kernels are
+            // bound by instruction issue on hub-heavy graphs (SQ counters,
             // profiles/r06_sq_reddit.txt; with both gathers folded to L2 hits the launch only drops from 1888 to 1474 us: DESIGN
             // section 5); the second exponential was libm's expf,
             // ~25 instructions per edge and lane.  The accumulator is rescaled only when some lane of the wave saw a new
@@ -278,17 +291,18 @@ struct GatFwdOp {
             for (int i = 0; i < VEC; ++i) s.acc[i] = fmaf(pw, b.v[u][i], s.acc[i]);
         }
     }
-    __device__ __forceinline__ void chunk_begin(Ctx &c, State &, int, int, int my_c, int sub, int, float *lds,
+    __device__ __forceinline__ void chunk_begin(Ctx &c, State &s, int, int, int my_c, int sub, int, float *lds,
                                                 const LaneVals &lv) const {
         chunk_scalars_load<ACH, A24>(c.cs, attn_col, my_c, sub, lds);
         c.lv = lv;
         c.sub = sub;
+        s.mx = gat_seen_edges(s.mx);  // (once per chunk, not per edge: a -inf score then meets a finite maximum in apply)
     }
     __device__ __forceinline__ void batch_end(const Ctx &, State &, int, int, int) const {}
     __device__ __forceinline__ void chunk_end(const Ctx &, State &, int, int) const {}
     __device__ __forceinline__ void row_end(const Ctx &c, const State &s, int64_t row, bool ok) const {
         if (ok && c.col_ok) {
-            const float inv = (s.lsum > 0.f) ? 1.f / s.lsum : 0.f;  // empty row -> zeros
+            const float inv = gat_row_scale(s.mx, s.lsum);
             float r[VEC];
 #pragma unroll
             for (int i = 0; i < VEC; ++i) r[i] = s.acc[i] * inv;
@@ -414,7 +428,7 @@ struct GatFwdChunkOp {
             lmax = fmaxf(lmax, sc);
         }
         lmax = head_max(lmax);
-        const float mn = fmaxf(s.mx, lmax);
+        const float mn = gat_seen_edges(fmaxf(s.mx, lmax));  // (finite: a chunk of nothing but -inf scores gives p = 0, not NaN)
         const float scale = (s.lsum == 0.f) ? 0.f : expf(s.mx - mn);
         float psum = 0.f;
         for (int r = 0; r < rounds; ++r) {
@@ -446,9 +460,10 @@ struct GatFwdChunkOp {
     __device__ __forceinline__ void chunk_end(const Ctx &, State &, int, int) const {}
     __device__ __forceinline__ void row_end(const Ctx &c, const State &s, int64_t row, bool ok) const {
         const float lsum_col = __shfl(s.lsum, c.lane0 + c.hd, kWave);  // (all lanes of the group take part)
+        const float mx_col = __shfl(s.mx, c.lane0 + c.hd, kWave);
         if (!ok) return;
         if (c.col_ok) {
-            const float inv = (lsum_col > 0.f) ? 1.f / lsum_col : 0.f;  // empty row -> zeros
+            const float inv = gat_row_scale(mx_col, lsum_col);
             float r[VEC];
 #pragma unroll
             for (int i = 0; i < VEC; ++i) r[i] = s.acc[i] * inv;

@@ -3,8 +3,10 @@
 // forward : out[r,c] = max_{e in row r} feat[colind[e],c], max_id[r,c] = colind of the FIRST
 //           maximum in CSR order; empty row -> 0 / -1.  (The reference starts from FLT_MIN --
 //           the smallest positive float -- so all-negative rows return 1.18e-38 with an
-//           uninitialised argmax; that is not reproduced.)  NaN never wins (`v > acc` is false),
-//           as in the reference's `acc < B`.
+//           uninitialised argmax; that is not reproduced.)  Non-finite values: out = the maximum over the row's
+//           non-NaN values (+inf and -inf are ordinary values), max_id = the colind of its first occurrence; a NaN never
+//           wins over a number, wherever it stands in the row.  Only a column whose values in the row are ALL NaN gives
+//           NaN, with the first edge's colind.
 // backward: grad_src[max_id[r,c], c] += grad[r,c] into a buffer zeroed here (the reference
 //           accumulates into torch::empty memory).  fp32 hardware atomics, one per element.
 // Same row-group decomposition, coalesced row gathers and long-row path as spmm.hip (engine: rowreduce.h).
@@ -12,8 +14,13 @@
 
 namespace cogdl {
 
+// v replaces the accumulator: it is larger, or it is a number and the accumulator is the NaN that a range's first edge
+// left there (the first edge of a range is taken unconditionally).  A NaN v never replaces anything.
+__device__ __forceinline__ bool beats(float v, float acc) { return !(v <= acc) && v == v; }
+
 // State = (running max, colind of its first occurrence) per column; two edge ranges merge by keeping the
-// earlier range's entry on ties, so the chunk-parallel path returns the same argmax as the sequential walk.
+// earlier range's entry on ties, so the chunk-parallel path returns the same argmax as the sequential walk.  A range whose
+// state is NaN held nothing but NaN, so the rule of `beats` gives the same result for every placement of the chunk borders.
 template <int VEC_, int LPR_, int UNROLL_>
 struct ScatterMaxOp {
     static constexpr int VEC = VEC_, LPR = LPR_, UNROLL = UNROLL_, kRec = 2 * VEC_;
@@ -66,7 +73,7 @@ struct ScatterMaxOp {
         if (valid) {
 #pragma unroll
             for (int i = 0; i < VEC; ++i) {
-                const bool take = (s.id[i] < 0) || (b.v[u][i] > s.acc[i]);
+                const bool take = (s.id[i] < 0) || beats(b.v[u][i], s.acc[i]);
                 s.acc[i] = take ? b.v[u][i] : s.acc[i];
                 s.id[i] = take ? b.c[u] : s.id[i];
             }
@@ -99,7 +106,7 @@ struct ScatterMaxOp {
     __device__ __forceinline__ void merge(const Ctx &, State &a, const State &b) const {
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
-            const bool take = b.id[i] >= 0 && ((a.id[i] < 0) || (b.acc[i] > a.acc[i]));
+            const bool take = b.id[i] >= 0 && ((a.id[i] < 0) || beats(b.acc[i], a.acc[i]));
             a.acc[i] = take ? b.acc[i] : a.acc[i];
             a.id[i] = take ? b.id[i] : a.id[i];
         }
