@@ -184,6 +184,14 @@ HIP_SIGNATURES = {
     "cogdl_hip_kg_score": ([_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _vp, _vp], _i32),
     "cogdl_hip_kg_score_grad_q": ([_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp], _i32),
     "cogdl_hip_kg_score_grad_table": ([_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp], _i32),
+    # WL subtree relabelling (csrc/wl.hip)
+    "cogdl_hip_wl_max_degree": ([], _i32),
+    "cogdl_hip_wl_workspace_bytes": ([_i64, _i64], _sz),
+    "cogdl_hip_wl_labels": ([_vp, _vp, _vp, _i64, _i64, _i64, _i32, _u64, _vp, _vp, _vp, _vp, _sz, _vp], _i32),
+    # PV-DBOW training (csrc/pvdbow.hip)
+    "cogdl_hip_pvdbow_init": ([_vp, _i64, _vp, _i64, _i32, _u64, _vp], _i32),
+    "cogdl_hip_pvdbow_train": ([_vp, _i64, _vp, _i64, _i64, _i32, _i32, _i64, _f64, _f64, _vp, _vp, _vp, _u64, _i32, _i64,
+                                _vp, _vp, _vp, _vp], _i32),
 }
 
 MAX_SEGMENTS = 64  # COGDL_HIP_MAX_SEGMENTS
@@ -223,6 +231,11 @@ HOST_SIGNATURES = {
     "cogdl_host_kg_score": ([_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _vp], _i32),
     "cogdl_host_kg_score_grad_q": ([_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp], _i32),
     "cogdl_host_kg_score_grad_table": ([_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp], _i32),
+    "cogdl_host_wl_max_degree": ([], _i32),
+    "cogdl_host_wl_labels": ([_vp, _vp, _vp, _i64, _i64, _i64, _i32, _u64, _vp, _vp, _vp], _i32),
+    "cogdl_host_pvdbow_init": ([_vp, _i64, _vp, _i64, _i32, _u64], _i32),
+    "cogdl_host_pvdbow_train": ([_vp, _i64, _vp, _i64, _i64, _i32, _i32, _i64, _f64, _f64, _vp, _vp, _vp, _u64, _i32,
+                                 _vp, _vp, _vp], _i32),
 }
 
 EUNSUPPORTED = 7  # COGDL_HIP_EUNSUPPORTED

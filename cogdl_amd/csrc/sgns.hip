@@ -31,6 +31,7 @@
 #include "common.h"
 
 #include "sgns_law.h"
+#include "sgns_mem.h"
 
 namespace cogdl {
 
@@ -53,25 +54,12 @@ struct SgnsJob {
     const int *flags;
 };
 
-__device__ __forceinline__ float row_load(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-template <bool STORES>
-__device__ __forceinline__ void row_add(float *p, float old, float delta) {
-    if constexpr (STORES) __hip_atomic_store(p, old + delta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else atomicAdd(p, delta);
-}
-
-// every vector memory operation of this wave has completed (vmcnt(0); expcnt and lgkmcnt left alone)
-__device__ __forceinline__ void wait_own_updates() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+// (row_load, row_add, wait_own_updates and uniform_f32 are sgns_mem.h's: pvdbow.hip follows the same rules)
 
 __device__ __forceinline__ void sgns_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ float uniform_f32(float v) {
-    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
 
 // Rows row0 + (global wave index) + k * (waves of the grid) below row0 + n_rows, for the epochs [e0, e1).

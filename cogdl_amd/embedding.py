@@ -7,6 +7,7 @@ library's skip-gram operator -- what the reference's DeepWalk / Node2vec do thro
     netsmf(graph_or_csr, dim, window, negative, rounds)                     -> float32 [N, dim]
     metapath2vec(graph_or_csr, node_type, schema, dim, walk_length, walk_num, window, epochs) -> float32 [N, dim]
     prone(graph_or_csr, dim, step, mu, theta)                               -> float32 [N, dim]
+    graph2vec(graphs, dim, rounds, min_count, epochs)                       -> float32 [G, dim]  (one row per graph)
 
 `graph_or_csr` is a cogdl Graph (its row_indptr / col_indices are used on the device they live on) or an
 (indptr, indices) pair of int64 tensors.  Each of the walk_num passes starts one walk at every node, in an order shuffled
@@ -113,6 +114,121 @@ def metapath2vec(graph_or_csr, node_type, schema, dim=128, walk_length=80, walk_
     syn0, _ = skipgram(walks, n, dim=dim, window=window, negative=negative, epochs=epochs, alpha=alpha, min_alpha=min_alpha,
                        sample=sample, seed=(seed + 2) & (2 ** 64 - 1), workers=workers)
     return (syn0, walks) if return_walks else syn0
+
+
+class DegreeCapError(ValueError):
+    """A node of the batch has more neighbours than wl_labels sorts in one workgroup."""
+
+
+def _edge_pair(edge_index):
+    row, col = (edge_index[0], edge_index[1])
+    return torch.as_tensor(row).long().flatten(), torch.as_tensor(col).long().flatten()
+
+
+def graph2vec_documents(graphs, rounds=2, device=None):
+    """The WL documents of a list of graphs (cogdl Graphs, or (edge_index, x_or_None) pairs) on `device` (default: the
+    device of the first graph's edges) -> (doc_ptr int64 [G + 1], token int64 [T], round int64 [T], node int64 [T], classes
+    int64 [rounds + 1]): graph g owns the positions [doc_ptr[g], doc_ptr[g + 1]), ordered by (round, node id); node ids are
+    the graph's own; token = classes[0] + .. + classes[round - 1] + labels[round][node] over the whole batch.
+
+    Per graph the edges are symmetrised and duplicates dropped (networkx's from_edgelist: undirected and simple, a
+    self-loop kept once); one batched CSR is built with the library's COO to CSR route.  Round-0 labels: with x the id of
+    the node's feature row (rows equal as float32 arrays share a label, across graphs), without x the networkx degree (a
+    self-loop counts 2).  In rounds 1..R the nodes that occur in an edge contribute; in round 0 every row of x does when x
+    is given, otherwise the same nodes -- as the reference's feature_extractor / wl_iterations do."""
+    from .graph_build import coo2csr_index
+    from .operators.wl import MAX_DEGREE, wl_labels
+
+    rounds = int(rounds)
+    if rounds < 0:
+        raise ValueError("graph2vec: rounds must be >= 0 (got %d)" % rounds)
+    pairs = []
+    for g in graphs:
+        if isinstance(g, (tuple, list)) and len(g) == 2:
+            pairs.append((g[0], g[1]))
+        else:
+            pairs.append((g.edge_index, getattr(g, "x", None)))
+    if not pairs:
+        raise ValueError("graph2vec: an empty list of graphs")
+    edges = [_edge_pair(ei) for ei, _ in pairs]
+    dev = torch.device(device) if device is not None else edges[0][0].device
+    n_graphs = len(pairs)
+    x_rows = torch.tensor([0 if x is None else int(x.shape[0]) for _, x in pairs], dtype=torch.long, device=dev)
+    has_x = torch.tensor([x is not None for _, x in pairs], dtype=torch.bool, device=dev)
+    n_edges = torch.tensor([r.numel() for r, _ in edges], dtype=torch.long, device=dev)
+    row = torch.cat([r for r, _ in edges]).to(dev)
+    col = torch.cat([c for _, c in edges]).to(dev)
+    if row.numel() and int(torch.minimum(row.min(), col.min())) < 0:
+        raise ValueError("graph2vec: a negative node id")
+    gid = torch.repeat_interleave(torch.arange(n_graphs, device=dev), n_edges)
+    top = torch.full((n_graphs,), -1, dtype=torch.long, device=dev)
+    top.scatter_reduce_(0, gid, torch.maximum(row, col), "amax")
+    if bool((has_x & (top >= x_rows)).any()):
+        raise ValueError("graph2vec: an edge names a node without a row of x")
+    n_nodes = torch.maximum(top + 1, x_rows)
+    first = torch.zeros(n_graphs + 1, dtype=torch.long, device=dev)
+    torch.cumsum(n_nodes, 0, out=first[1:])
+    total = int(first[-1])
+    graph_of = torch.repeat_interleave(torch.arange(n_graphs, device=dev), n_nodes)
+    # the simple undirected structure of the batch
+    a, b = row + first[gid], col + first[gid]
+    keys = torch.unique(torch.cat([a * total + b, b * total + a]))
+    src, dst = keys // max(total, 1), keys % max(total, 1)
+    indptr, perm = coo2csr_index(src, dst, total)
+    indices = dst[perm]
+    deg = indptr[1:] - indptr[:-1]
+    if total and int(deg.max()) > MAX_DEGREE:
+        raise DegreeCapError("graph2vec: a node has %d neighbours, more than %d" % (int(deg.max()), MAX_DEGREE))
+    in_edge = deg > 0
+    loops = torch.zeros(total, dtype=torch.long, device=dev)
+    loops[src[src == dst]] = 1
+    label0 = (deg + loops) * 2  # the networkx degree; even, feature-row ids are odd
+    if bool(has_x.any()):
+        widths = set(int(x.shape[1]) if x.dim() == 2 else -1 for _, x in pairs if x is not None)
+        if len(widths) != 1 or -1 in widths:
+            raise ValueError("graph2vec: x must be 2-D with one width over the batch")
+        feats = torch.cat([x.to(dev).float() for _, x in pairs if x is not None])
+        row_id = torch.unique(feats, dim=0, return_inverse=True)[1]
+        node_has_x = has_x[graph_of]
+        # (a graph with x has exactly x_rows nodes, so its rows are its nodes in order)
+        label0 = label0.clone()
+        label0[node_has_x] = row_id * 2 + 1
+    else:
+        node_has_x = torch.zeros(total, dtype=torch.bool, device=dev)
+    labels, classes = wl_labels(indptr.int().contiguous(), indices.int().contiguous(), label0, rounds)
+    offset = torch.cumsum(classes, 0) - classes
+    local = torch.arange(total, device=dev) - first[graph_of]
+    tok, rnd, node, doc = [], [], [], []
+    for r in range(rounds + 1):
+        mask = in_edge | node_has_x if r == 0 else in_edge
+        tok.append(offset[r] + labels[r][mask].long())
+        rnd.append(torch.full((int(mask.sum()),), r, dtype=torch.long, device=dev))
+        node.append(local[mask])
+        doc.append(graph_of[mask])
+    tok, rnd, node, doc = torch.cat(tok), torch.cat(rnd), torch.cat(node), torch.cat(doc)
+    order = torch.sort(doc, stable=True)[1]  # (rounds follow each other, nodes ascend inside one: (graph, round, node))
+    doc_ptr = torch.zeros(n_graphs + 1, dtype=torch.long, device=dev)
+    torch.cumsum(torch.bincount(doc, minlength=n_graphs), 0, out=doc_ptr[1:])
+    return doc_ptr, tok[order].contiguous(), rnd[order], node[order], classes
+
+
+def graph2vec(graphs, dim=128, rounds=2, min_count=5, epochs=10, alpha=0.025, sample=0.0, negative=5, seed=None, workers=0,
+              device=None):
+    """Graph2Vec: WL subtree words per graph (graph2vec_documents), a vocabulary of the words seen at least min_count times
+    (ids compacted by a prefix sum; a dropped word becomes padding), then PV-DBOW.  -> float32 [G, dim] on `device`.  A graph
+    none of whose words is kept keeps its initial vector."""
+    from .operators.pvdbow import doc2vec_dbow, init_tables
+
+    doc_ptr, tok, _, _, classes = graph2vec_documents(graphs, rounds, device)
+    n_tokens = int(classes.sum())
+    keep = torch.bincount(tok, minlength=max(n_tokens, 1)) >= max(int(min_count), 1)
+    if not bool(keep.any()):  # nothing to train on
+        return init_tables(doc_ptr.numel() - 1, 1, int(dim), _seed(seed), doc_ptr.device)[0]
+    new_id = torch.cumsum(keep, 0) - 1
+    words = torch.where(keep[tok], new_id[tok], torch.full_like(tok, -1)) if tok.numel() else tok
+    dv, _ = doc2vec_dbow(doc_ptr, words.contiguous(), max(int(keep.sum()), 1), dim=dim, negative=negative, epochs=epochs, alpha=alpha,
+                         sample=sample, seed=seed, workers=workers)
+    return dv
 
 
 def netsmf(graph_or_csr, dim=128, window=10, negative=1, rounds=100, seed=None):

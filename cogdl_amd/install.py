@@ -41,7 +41,7 @@ _finder = None
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
             metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False, readout=False,
             relational=False, genconv=False, disengcn=False, contrast=False, netsmf=False, metapath=False, prone=False,
-            kg_eval=False, kg_train=False):
+            kg_eval=False, kg_train=False, graph2vec=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -166,6 +166,14 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     entity table is a sum in a fixed order instead of an atomic scatter, equal from run to run.  The loss, the self-adversarial
     softmax and the regulariser stay the reference's.  Any other model class, a subclass with its own `score` and an unknown
     mode reach the reference's forward.  Not for use under torch.cuda.graph capture.
+    graph2vec=True rebinds Graph2Vec.forward in cogdl.models.emb.graph2vec (opt-in: the draws are Philox's, the vocabulary is not
+    gensim's, and feature rows are compared as float32 arrays, not as numpy's printed strings) to cogdl_amd.graph2vec_compat: one
+    batched CSR of all graphs is built on their device (or on the GPU when one is visible), the WL subtree words come from the
+    library's wl_labels operator (HIP kernels for a CSR on the GPU, the host twin otherwise) instead of an md5 per node and round
+    over networkx adjacency, and the library's doc2vec_dbow operator trains PV-DBOW on them; the return value is the
+    reference's (a numpy array with one row per graph).  The reference module imports gensim.models.doc2vec, so where gensim is
+    absent cogdl_amd.gensim_compat is registered first, as metapath=True does.  A dm that selects PV-DM, an x that is not a
+    numeric tensor, an empty list and a node over wl_labels' degree cap reach the reference's forward.
     linear=True additionally routes torch.nn.functional.linear -- i.e. the unchanged nn.Linear inside every CogDL
     layer -- through cogdl_amd.linear (hand-written MFMA weight gradient for full-graph shapes)."""
     global _finder
@@ -289,7 +297,14 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
             _import_target(name, "kg_train")
         if not kgtrain_compat.install():
             raise _lib_error("install(kg_train=True): KGEModel.forward could not be rebound")
-    su = sys.modules.get("cogdl.utils.spmm_utils")
+    if graph2vec:
+        from . import graph2vec_compat
+
+        _serve_gensim_where_absent()  # (cogdl.models.emb.graph2vec imports gensim.models.doc2vec)
+        _import_target(graph2vec_compat._MODULE, "graph2vec")
+        if not graph2vec_compat.install():
+            raise _lib_error("install(graph2vec=True): Graph2Vec.forward could not be rebound")
+    su =sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):
             su.CONFIGS[k] = False

@@ -34,6 +34,9 @@
 
     kgscore.py       sampled_scores (also exported here)               (KGEModel.forward, models/emb/knowledge_base.py:52-101)
 
+    wl.py            wl_labels (also exported here)                    (Graph2Vec.wl_iterations, models/emb/graph2vec.py:63-78)
+    pvdbow.py        doc2vec_dbow (also exported here)                 (gensim's Doc2Vec(dm=0) in models/emb/graph2vec.py:99-109)
+
     ops.py           scatter_add, op_aggr, s_*_e_sum / s_*_e_mean (fused HIP), s_*_e, s_*_t   (cogdl/operators/ops.py)
 
 Submodules are imported lazily: GPU modules load libcogdl_hip.so at import and raise if it
@@ -90,4 +93,12 @@ def __getattr__(name):
         from . import kgscore
 
         return kgscore.sampled_scores
+    if name == "wl_labels":
+        from . import wl
+
+        return wl.wl_labels
+    if name == "doc2vec_dbow":
+        from . import pvdbow
+
+        return pvdbow.doc2vec_dbow
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

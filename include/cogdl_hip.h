@@ -1223,6 +1223,54 @@ COGDL_API int cogdl_hip_kg_score_grad_table(const float *q, const float *table, 
                        const int32_t *occ_pos, int64_t B, int64_t K, int64_t N, int64_t D, int kind, float *grad_table,
                        void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Weisfeiler-Lehman subtree relabelling on a batch of graphs (added within ABI v9: new symbols only; csrc/wl.hip): the
+ * refinement of Graph2Vec.wl_iterations (cogdl/models/emb/graph2vec.py:63-78) as integers.  The law is csrc/wl_law.h; the
+ * host twin is cogdl_host_wl_labels and returns the same bytes.
+ *   indptr, indices   int32 CSR [N + 1] / [E] of the disjoint union of the graphs, taken as given (multiplicity counts, a
+ *                self-loop is a neighbour).  N <= 2^30, E < 2^31.
+ *   label0       int64 [N], arbitrary values.
+ *   labels       int32 [rounds + 1, N]: labels[r][v] = the number of classes of round r whose first node precedes the first
+ *                node of v's class.  classes int64 [rounds + 1]: the number of classes per round.
+ *   hash_bits    1..128: the per-node hash is cut to that many bits before it is used (128: the whole hash).  A test hook:
+ *                the result is exact either way, because every node is verified against its representative.  salt: any.
+ *   *flags       device int, zeroed by the call: 1 a malformed indptr, 2 an index outside [0, N), 4 a row of more than
+ *                cogdl_hip_wl_max_degree() = 32768 neighbours (these three: nothing is computed), 8 two different signatures
+ *                with one hash, 16 the probe bound of the table.  Non-zero marks an invalid result; nothing is read out of
+ *                bounds and every device loop is bounded.
+ *   Enqueues on `stream`, allocates nothing, does not synchronise; ws: cogdl_hip_wl_workspace_bytes(N, E) bytes, 16-byte
+ *   aligned.  Not for use under stream capture.
+ * ------------------------------------------------------------------------------------------------------------------- */
+COGDL_API int cogdl_hip_wl_max_degree(void);
+COGDL_API size_t cogdl_hip_wl_workspace_bytes(int64_t N, int64_t E);
+COGDL_API int cogdl_hip_wl_labels(const int32_t *indptr, const int32_t *indices, const int64_t *label0, int64_t N, int64_t E,
+                       int64_t rounds, int hash_bits, uint64_t salt, int32_t *labels, int64_t *classes, int *flags, void *ws,
+                       size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * PV-DBOW training over ragged documents (added within ABI v9: new symbols only; csrc/pvdbow.hip): the trainer behind gensim's
+ * Doc2Vec(dm=0, negative=K) as cogdl/models/emb/graph2vec.py:99-109 calls it.  The law is csrc/pvdbow_law.h on top of
+ * csrc/sgns_law.h.  Host twins: cogdl_host_pvdbow_init / cogdl_host_pvdbow_train.
+ *   doc_ptr      int64 [G + 1], non-decreasing, within [0, T]: document g owns words[doc_ptr[g] .. doc_ptr[g + 1]).
+ *   words        int64 [T], ids in [0, V); a negative id is padding.  No cap on a document's length below 2^32.
+ *   D, negative  1..512, 1..16.  epochs >= 1.  keep, cum, exp_table, alpha, min_alpha as for cogdl_hip_sgns_train; the
+ *                learning rate falls over epochs * G documents.
+ *   dv           float [G, D], syn1 float [V, D], read and updated in place (cogdl_hip_pvdbow_init fills dv from the seed
+ *                and zeroes syn1).
+ *   workers      1: one launch of one wave, documents in order; equals the host twin bit for bit.  Anything else: launches
+ *                of at most docs_in_flight documents (0 = the library's default, 8192) in document order, one wave per
+ *                document; syn1 is updated without locks, a dv row has one writer.
+ *   *flags       device int, zeroed by the call, then set by a validation pass that runs before any update: 1 an id >= V,
+ *                2 a cum that runs backwards or ends in 0, 4 a doc_ptr below 0, running backwards or past T.  Non-zero: the
+ *                tables were not touched.  Nothing is read out of bounds.
+ *   Stream-ordered, allocates nothing, does not synchronise.  Tuning key 17 selects the row update as for sgns.
+ * ------------------------------------------------------------------------------------------------------------------- */
+COGDL_API int cogdl_hip_pvdbow_init(float *dv, int64_t G, float *syn1, int64_t V, int D, uint64_t seed, void *stream);
+COGDL_API int cogdl_hip_pvdbow_train(const int64_t *doc_ptr, int64_t G, const int64_t *words, int64_t T, int64_t V, int D,
+                       int negative, int64_t epochs, double alpha, double min_alpha, const uint32_t *keep,
+                       const uint32_t *cum, const float *exp_table, uint64_t seed, int workers, int64_t docs_in_flight,
+                       float *dv, float *syn1, int *flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

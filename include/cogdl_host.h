@@ -207,6 +207,27 @@ COGDL_HOST_API int cogdl_host_kg_score_grad_table(const float *q, const float *t
                                                   const int32_t *occ_pos, int64_t B, int64_t K, int64_t N, int64_t D, int kind,
                                                   float *grad_table);
 
+/* Weisfeiler-Lehman subtree relabelling; the host twin of cogdl_hip_wl_labels (include/cogdl_hip.h, where the contract is
+ * spelled out): same arguments minus the workspace and the stream, all pointers host memory.  Signatures are compared
+ * outright, so the result never depends on a hash; labels and classes are EXACTLY the GPU's.  hash_bits < 128 emulates the
+ * GPU's truncated hash: *flags gets bit 3 (8) where two different signatures of a round share the truncated hash, which is
+ * where the GPU's verification raises it.  The same degree cap applies (bit 2).  The result does not depend on the number
+ * of threads. */
+COGDL_HOST_API int cogdl_host_wl_max_degree(void);
+COGDL_HOST_API int cogdl_host_wl_labels(const int32_t *indptr, const int32_t *indices, const int64_t *label0, int64_t N,
+                                        int64_t E, int64_t rounds, int hash_bits, uint64_t salt, int32_t *labels,
+                                        int64_t *classes, int *flags);
+
+/* PV-DBOW training; the host twins of cogdl_hip_pvdbow_init / cogdl_hip_pvdbow_train (include/cogdl_hip.h): same arguments
+ * minus docs_in_flight and the stream, all pointers host memory.  workers == 1 is strictly sequential and returns EXACTLY
+ * the tables of the GPU's serial mode (both run csrc/pvdbow_law.h); workers == 0 (OpenMP's default thread count) or > 1
+ * runs the documents of an epoch in parallel without locks. */
+COGDL_HOST_API int cogdl_host_pvdbow_init(float *dv, int64_t G, float *syn1, int64_t V, int D, uint64_t seed);
+COGDL_HOST_API int cogdl_host_pvdbow_train(const int64_t *doc_ptr, int64_t G, const int64_t *words, int64_t T, int64_t V, int D,
+                                           int negative, int64_t epochs, double alpha, double min_alpha, const uint32_t *keep,
+                                           const uint32_t *cum, const float *exp_table, uint64_t seed, int workers, float *dv,
+                                           float *syn1, int *flags);
+
 #ifdef __cplusplus
 }
 #endif
