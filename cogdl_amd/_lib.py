@@ -16,7 +16,7 @@ HOST_LIB_PATH = os.path.join(_CSRC, "libcogdl_host.so")
 
 _vp, _i64, _i32, _f32, _sz, _u64 = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float,
                                      ctypes.c_size_t, ctypes.c_uint64)
-_f64 = ctypes.c_double
+_f64, _u32 = ctypes.c_double, ctypes.c_uint32
 
 # name -> (argtypes, restype): must list every symbol declared in include/cogdl_hip.h
 HIP_SIGNATURES = {
@@ -192,6 +192,9 @@ HIP_SIGNATURES = {
     "cogdl_hip_pvdbow_init": ([_vp, _i64, _vp, _i64, _i32, _u64, _vp], _i32),
     "cogdl_hip_pvdbow_train": ([_vp, _i64, _vp, _i64, _i64, _i32, _i32, _i64, _f64, _f64, _vp, _vp, _vp, _u64, _i32, _i64,
                                 _vp, _vp, _vp, _vp], _i32),
+    # knowledge-graph training batches (csrc/kgsample.hip)
+    "cogdl_hip_kg_train_batch": ([_vp] * 5 + [_i64, _i64, _i64, _vp, _i64, _i64, _i64, _u64, _u32, _u64, _i32, _vp, _vp, _vp, _vp,
+                                  _vp], _i32),
 }
 
 MAX_SEGMENTS = 64  # COGDL_HIP_MAX_SEGMENTS
@@ -236,6 +239,8 @@ HOST_SIGNATURES = {
     "cogdl_host_pvdbow_init": ([_vp, _i64, _vp, _i64, _i32, _u64], _i32),
     "cogdl_host_pvdbow_train": ([_vp, _i64, _vp, _i64, _i64, _i32, _i32, _i64, _f64, _f64, _vp, _vp, _vp, _u64, _i32,
                                  _vp, _vp, _vp], _i32),
+    "cogdl_host_kg_train_batch": ([_vp] * 5 + [_i64, _i64, _i64, _vp, _i64, _i64, _i64, _u64, _u32, _u64, _i32, _vp, _vp, _vp, _vp],
+                                  _i32),
 }
 
 EUNSUPPORTED = 7  # COGDL_HIP_EUNSUPPORTED

@@ -41,7 +41,7 @@ _finder = None
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
             metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False, readout=False,
             relational=False, genconv=False, disengcn=False, contrast=False, netsmf=False, metapath=False, prone=False,
-            kg_eval=False, kg_train=False, graph2vec=False):
+            kg_eval=False, kg_train=False, graph2vec=False, kg_sample=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -174,6 +174,17 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     reference's (a numpy array with one row per graph).  The reference module imports gensim.models.doc2vec, so where gensim is
     absent cogdl_amd.gensim_compat is registered first, as metapath=True does.  A dm that selects PV-DM, an x that is not a
     numeric tensor, an empty list and a node over wl_labels' degree cap reach the reference's forward.
+    kg_sample=True rebinds TripleDataWrapper.train_wrapper in
+    cogdl.wrappers.data_wrapper.link_prediction.triple_link_prediction_dw (opt-in: the negatives are drawn by this library's
+    Philox law, csrc/kgsample_law.h, seeded with torch.initial_seed(), not by numpy's global generator -- the distribution is the
+    same, uniform with repetition over the entities that are not true for the positive, and the numbers are not) to
+    cogdl_amd.kgsample_compat: the iterator the trainer hands to TripleModelWrapper.train_step is cogdl_amd.kgsample.TrainBatches
+    instead of BidirectionalOneShotIterator over two DataLoaders.  The true-head and true-tail lists and the subsampling weights
+    (bit-equal to the reference's) are flat tables built once with torch sort / unique on the triples' device, and every batch --
+    positive int64 [b, 3], negative int64 [b, K], subsampling_weight float32 [b], mode, "tail-batch" first -- is one launch of
+    the library's negative_batch operator on the training device (HIP kernel for tables on the GPU, the OpenMP host twin
+    otherwise) without a rejection loop, a collate or a host-to-device copy.  A dataset without `triples`, `train_start_idx`,
+    `valid_start_idx` and `_num_entities` reaches the reference's method.
     linear=True additionally routes torch.nn.functional.linear -- i.e. the unchanged nn.Linear inside every CogDL
     layer -- through cogdl_amd.linear (hand-written MFMA weight gradient for full-graph shapes)."""
     global _finder
@@ -304,6 +315,12 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
         _import_target(graph2vec_compat._MODULE, "graph2vec")
         if not graph2vec_compat.install():
             raise _lib_error("install(graph2vec=True): Graph2Vec.forward could not be rebound")
+    if kg_sample:
+        from . import kgsample_compat
+
+        _import_target(kgsample_compat._MODULE, "kg_sample")
+        if not kgsample_compat.install():
+            raise _lib_error("install(kg_sample=True): TripleDataWrapper.train_wrapper could not be rebound")
     su =sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):

@@ -34,6 +34,9 @@
 
     kgscore.py       sampled_scores (also exported here)               (KGEModel.forward, models/emb/knowledge_base.py:52-101)
 
+    kgsample.py      negative_batch (also exported here)               (TrainDataset.__getitem__ / collate_fn,
+                                                                        cogdl/datasets/kg_data.py:98-135)
+
     wl.py            wl_labels (also exported here)                    (Graph2Vec.wl_iterations, models/emb/graph2vec.py:63-78)
     pvdbow.py        doc2vec_dbow (also exported here)                 (gensim's Doc2Vec(dm=0) in models/emb/graph2vec.py:99-109)
 
@@ -93,6 +96,10 @@ def __getattr__(name):
         from . import kgscore
 
         return kgscore.sampled_scores
+    if name == "negative_batch":
+        from . import kgsample
+
+        return kgsample.negative_batch
     if name == "wl_labels":
         from . import wl
 

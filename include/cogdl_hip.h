@@ -1271,6 +1271,35 @@ COGDL_API int cogdl_hip_pvdbow_train(const int64_t *doc_ptr, int64_t G, const in
                        const uint32_t *cum, const float *exp_table, uint64_t seed, int workers, int64_t docs_in_flight,
                        float *dv, float *syn1, int *flags, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * One training batch of a knowledge-graph embedding model (added within ABI v9: new symbols only; csrc/kgsample.hip): for
+ * each of the B positives `order` names, the triple, its subsampling weight and K negatives drawn uniformly, with
+ * repetition, from the entities that are not in the positive's true list -- the batch TrainDataset.__getitem__ and collate_fn
+ * make on the host (cogdl/datasets/kg_data.py:98-135).  The law is csrc/kgsample_law.h: negative j of the positive with
+ * ordinal sid = first_sid + b (modulo 2^64) is a pure function of (seed, tag, sid, j) and the list; no rejection loop.  The
+ * host twin is cogdl_host_kg_train_batch and returns the same bytes.
+ *   triples      int32 [T, 3] (head, relation, tail); weight_tab float [T]; group int32 [T]: the list of each triple.
+ *   list_ptr     int32 [G + 1], list_idx int32 [list_len]: list g is list_idx[list_ptr[g] .. list_ptr[g + 1]), ids in [0, N)
+ *                ascending and distinct (the true heads of a (relation, tail) for a head-batch, the true tails of a
+ *                (head, relation) for a tail-batch).
+ *   order        int32 [B]: the triple ids of this batch.  tag: COGDL_HIP_KG_TAG_HEAD or _TAIL (any word is accepted: it
+ *                only separates streams).
+ *   positive     int64 [B, 3]; negative [B, K], int64 where index64 is non-zero and int32 otherwise; weight float [B].
+ *   *status      device int, zeroed by the call: 1 an order id outside [0, T), 2 a list that leaves no entity free, 4 a group
+ *                id or list bounds outside the tables.  The row concerned is written as -1 (weight 0) and nothing is indexed
+ *                with the offending value; every other row is unaffected.  A list that is not ascending and distinct gives
+ *                wrong numbers, never an access outside the operands.
+ * Launches on `stream`; no workspace, no allocation, no synchronisation, no host read.  A negative size: COGDL_HIP_EINVAL;
+ * sizes of 2^31 - 1 and more: COGDL_HIP_ERANGE; B == 0: the status is zeroed, nothing else is launched; a NULL pointer to a
+ * non-empty operand: COGDL_HIP_EINVAL; pointers aligned to their element size (COGDL_HIP_EALIGN otherwise).
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define COGDL_HIP_KG_TAG_HEAD 0x4B474E48u
+#define COGDL_HIP_KG_TAG_TAIL 0x4B474E54u
+COGDL_API int cogdl_hip_kg_train_batch(const int32_t *triples, const float *weight_tab, const int32_t *group,
+                       const int32_t *list_ptr, const int32_t *list_idx, int64_t T, int64_t G, int64_t list_len,
+                       const int32_t *order, int64_t B, int64_t K, int64_t N, uint64_t seed, uint32_t tag, uint64_t first_sid,
+                       int index64, int64_t *positive, void *negative, float *weight, int *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

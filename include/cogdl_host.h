@@ -228,6 +228,17 @@ COGDL_HOST_API int cogdl_host_pvdbow_train(const int64_t *doc_ptr, int64_t G, co
                                            const uint32_t *cum, const float *exp_table, uint64_t seed, int workers, float *dv,
                                            float *syn1, int *flags);
 
+/* One training batch of a knowledge-graph embedding model; the host twin of cogdl_hip_kg_train_batch (include/cogdl_hip.h,
+ * where the contract is spelled out): same arguments minus the stream, all pointers host memory, no alignment requirement.
+ * Both sides follow csrc/kgsample_law.h, so for equal inputs positive, negative, weight and *status are EXACTLY the GPU's.
+ * OpenMP over the rows of the batch; the result does not depend on the number of threads.  Sizes of 2^31 - 1 and more:
+ * COGDL_HOST_ERANGE. */
+COGDL_HOST_API int cogdl_host_kg_train_batch(const int32_t *triples, const float *weight_tab, const int32_t *group,
+                                             const int32_t *list_ptr, const int32_t *list_idx, int64_t T, int64_t G,
+                                             int64_t list_len, const int32_t *order, int64_t B, int64_t K, int64_t N,
+                                             uint64_t seed, uint32_t tag, uint64_t first_sid, int index64, int64_t *positive,
+                                             void *negative, float *weight, int *status);
+
 #ifdef __cplusplus
 }
 #endif
