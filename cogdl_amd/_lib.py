@@ -195,6 +195,9 @@ HIP_SIGNATURES = {
     # knowledge-graph training batches (csrc/kgsample.hip)
     "cogdl_hip_kg_train_batch": ([_vp] * 5 + [_i64, _i64, _i64, _vp, _i64, _i64, _i64, _u64, _u32, _u64, _i32, _vp, _vp, _vp, _vp,
                                   _vp], _i32),
+    # edge-sampled skip-gram training, LINE orders 1 and 2 (csrc/line.hip)
+    "cogdl_hip_line_train": ([_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _i64, _f64, _u64, _i32, _i64, _vp, _vp, _vp,
+                              _vp], _i32),
 }
 
 MAX_SEGMENTS = 64  # COGDL_HIP_MAX_SEGMENTS
@@ -241,6 +244,8 @@ HOST_SIGNATURES = {
                                  _vp, _vp, _vp], _i32),
     "cogdl_host_kg_train_batch": ([_vp] * 5 + [_i64, _i64, _i64, _vp, _i64, _i64, _i64, _u64, _u32, _u64, _i32, _vp, _vp, _vp, _vp],
                                   _i32),
+    "cogdl_host_line_train": ([_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _i64, _f64, _u64, _i32, _vp, _vp, _vp, _vp,
+                               _i64, _vp], _i32),
 }
 
 EUNSUPPORTED = 7  # COGDL_HIP_EUNSUPPORTED

@@ -8,6 +8,7 @@ library's skip-gram operator -- what the reference's DeepWalk / Node2vec do thro
     metapath2vec(graph_or_csr, node_type, schema, dim, walk_length, walk_num, window, epochs) -> float32 [N, dim]
     prone(graph_or_csr, dim, step, mu, theta)                               -> float32 [N, dim]
     graph2vec(graphs, dim, rounds, min_count, epochs)                       -> float32 [G, dim]  (one row per graph)
+    line(graph_or_csr, dim, walk_length, walk_num, negative, alpha, order)  -> float32 [N, dim]
 
 `graph_or_csr` is a cogdl Graph (its row_indptr / col_indices are used on the device they live on) or an
 (indptr, indices) pair of int64 tensors.  Each of the walk_num passes starts one walk at every node, in an order shuffled
@@ -22,6 +23,9 @@ matrix, the sparsifier's log transform, a randomized SVD -- all three from cogdl
 prone is the other one (cogdl/models/emb/prone.py): an elementwise transform of the adjacency's entries, the same randomized
 SVD, the spectral propagation of cogdl_amd/operators/spectral.py (one fused filter step per sparse product) and a dense
 embedding from the [dim, dim] Gram matrix.
+
+line is the edge-sampling member (cogdl/models/emb/line.py): no walks, walk_length * walk_num * N edge samples trained by
+cogdl_amd/operators/line.py, orders 1 and 2 side by side for order 3.
 """
 import math
 
@@ -324,3 +328,59 @@ def prone(graph_or_csr, dim=128, step=5, mu=0.2, theta=0.5, seed=None):
     if step == 1:
         return feat
     return dense_embedding(spectral_filter("prone", rowptr, col, feat, order=step, mu=mu, s=theta))
+
+
+def undirected_edges(row, col, num_nodes, weight=None):
+    """The undirected edge table of (row, col) on their device -> (edges int64 [M, 2] with edges[:, 0] <= edges[:, 1], weight
+    float64 [M] or None): one entry per unordered pair, pairs ascending.  Where a pair repeats, the weight of its last
+    occurrence wins, as networkx's add_weighted_edges_from overwrites (Graph.to_networkx, cogdl/data/data.py:424-437)."""
+    row, col = torch.as_tensor(row).long().flatten(), torch.as_tensor(col).long().flatten()
+    lo, hi = torch.minimum(row, col), torch.maximum(row, col)
+    pairs, inverse = torch.unique(lo * num_nodes + hi, return_inverse=True)
+    edges = torch.stack([pairs // num_nodes, pairs % num_nodes], dim=1).contiguous()
+    if weight is None:
+        return edges, None
+    last = torch.zeros(pairs.numel(), dtype=torch.long, device=pairs.device)
+    last.scatter_reduce_(0, inverse, torch.arange(row.numel(), device=pairs.device), "amax", include_self=False)
+    return edges, torch.as_tensor(weight).to(pairs.device).double().flatten()[last]
+
+
+def _unit_rows(x):
+    norm = x.norm(dim=1, keepdim=True)
+    return torch.where(norm > 0, x / norm.clamp_min(1e-30), torch.zeros_like(x))
+
+
+def line_from_edges(edges, num_nodes, edge_weight=None, dim=128, samples=0, negative=5, alpha=0.025, order=3, seed=None, workers=0):
+    """LINE on an undirected edge table (int64 [M, 2], optional weights [M]) -> float32 [num_nodes, width], rows
+    L2-normalised (a zero row stays zero, as sklearn.preprocessing.normalize leaves it): width = dim for orders 1 and 2; order
+    3 trains order 1 and then order 2 at dim // 2 each and puts the two normalised halves side by side, width 2 * (dim // 2)."""
+    from .operators.line import line_train
+
+    order, dim = int(order), int(dim)
+    if order not in (1, 2, 3):
+        raise ValueError("line: order must be 1, 2 or 3 (got %d)" % order)
+    if order == 3 and dim < 2:
+        raise ValueError("line: order 3 needs dim >= 2 (got %d)" % dim)
+    seed = _seed(seed)
+    width = dim // 2 if order == 3 else dim
+    halves = []
+    for k, o in enumerate((1, 2) if order == 3 else (order,)):
+        out = line_train(edges, num_nodes, width, o, samples, negative=negative, alpha=alpha, edge_weight=edge_weight,
+                         seed=(seed + k) & (2 ** 64 - 1), workers=workers)
+        halves.append(_unit_rows(out if o == 1 else out[0]))
+    return halves[0] if len(halves) == 1 else torch.cat(halves, dim=1)
+
+
+def line(graph_or_csr, dim=128, walk_length=80, walk_num=20, negative=5, alpha=0.025, order=3, seed=None, edge_weight=None,
+         workers=0):
+    """LINE: walk_length * walk_num * N edge samples per order, each an edge drawn in proportion to its weight, oriented by a
+    fair coin, with `negative` negatives drawn in proportion to (weighted degree)^0.75 (cogdl_amd/operators/line.py).  The
+    graph is taken as undirected: one edge per unordered pair of the structure; `edge_weight` ([E], in the order of the CSR's
+    entries) gives a pair the weight of its last entry.  -> float32 [N, dim] on the graph's device, [N, 2 * (dim // 2)] for
+    order 3."""
+    indptr, indices = _csr(graph_or_csr)
+    n = indptr.numel() - 1
+    row = torch.repeat_interleave(torch.arange(n, device=indptr.device), indptr[1:] - indptr[:-1])
+    edges, weight = undirected_edges(row, indices, n, edge_weight)
+    return line_from_edges(edges, n, weight, dim=dim, samples=int(walk_length) * int(walk_num) * n, negative=negative, alpha=alpha,
+                           order=order, seed=seed, workers=workers)

@@ -41,7 +41,7 @@ _finder = None
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
             metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False, readout=False,
             relational=False, genconv=False, disengcn=False, contrast=False, netsmf=False, metapath=False, prone=False,
-            kg_eval=False, kg_train=False, graph2vec=False, kg_sample=False):
+            kg_eval=False, kg_train=False, graph2vec=False, kg_sample=False, line=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -185,6 +185,17 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     the library's negative_batch operator on the training device (HIP kernel for tables on the GPU, the OpenMP host twin
     otherwise) without a rejection loop, a collate or a host-to-device copy.  A dataset without `triples`, `train_start_idx`,
     `valid_start_idx` and `_num_entities` reaches the reference's method.
+    line=True rebinds LINE.forward in cogdl.models.emb.line (opt-in: the update is the original LINE program's, not the
+    reference's -- the reference's `_update` changes fancy-indexed copies, so it never updates a target or context row and its
+    orders 1 and 2 are one computation; here target rows are updated and the order-2 context table starts at zero -- the draws
+    are Philox's by inverse CDF, not numpy's through alias tables, the learning rate changes with every sample, a negative
+    equal to either endpoint is skipped, `batch_size` is ignored, `self.dimension` is not halved by a call with order 3, and
+    weighted degrees stay float64) to cogdl_amd.line_compat: the undirected edge table networkx would hold is built on the
+    graph's device with torch sort / unique, and the walk_length * walk_num * N samples per order run on the library's
+    line_train operator (HIP kernel for a graph on the GPU, the OpenMP host twin otherwise) instead of an interpreted
+    alias_draw per edge and per negative; the return value is the reference's (float64 numpy [N, width] with L2-normalised
+    rows, or the dict with return_dict=True).  Edge weights that are not all finite and positive, a graph without edges, an
+    order outside {1, 2, 3} and dimension < 2 with order 3 reach the reference's forward.
     linear=True additionally routes torch.nn.functional.linear -- i.e. the unchanged nn.Linear inside every CogDL
     layer -- through cogdl_amd.linear (hand-written MFMA weight gradient for full-graph shapes)."""
     global _finder
@@ -321,6 +332,12 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
         _import_target(kgsample_compat._MODULE, "kg_sample")
         if not kgsample_compat.install():
             raise _lib_error("install(kg_sample=True): TripleDataWrapper.train_wrapper could not be rebound")
+    if line:
+        from . import line_compat
+
+        _import_target(line_compat._MODULE, "line")
+        if not line_compat.install():
+            raise _lib_error("install(line=True): LINE.forward could not be rebound")
     su =sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):

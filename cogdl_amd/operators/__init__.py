@@ -39,6 +39,7 @@
 
     wl.py            wl_labels (also exported here)                    (Graph2Vec.wl_iterations, models/emb/graph2vec.py:63-78)
     pvdbow.py        doc2vec_dbow (also exported here)                 (gensim's Doc2Vec(dm=0) in models/emb/graph2vec.py:99-109)
+    line.py          line_train (also exported here)                   (LINE._train_line, models/emb/line.py:127-158)
 
     ops.py           scatter_add, op_aggr, s_*_e_sum / s_*_e_mean (fused HIP), s_*_e, s_*_t   (cogdl/operators/ops.py)
 
@@ -108,4 +109,8 @@ def __getattr__(name):
         from . import pvdbow
 
         return pvdbow.doc2vec_dbow
+    if name == "line_train":
+        from . import line
+
+        return line.line_train
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

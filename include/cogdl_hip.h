@@ -1300,6 +1300,34 @@ COGDL_API int cogdl_hip_kg_train_batch(const int32_t *triples, const float *weig
                        const int32_t *order, int64_t B, int64_t K, int64_t N, uint64_t seed, uint32_t tag, uint64_t first_sid,
                        int index64, int64_t *positive, void *negative, float *weight, int *status, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Edge-sampled skip-gram training with negative sampling (added within ABI v9: a new symbol only; csrc/line.hip): the
+ * trainer of the LINE model, orders 1 and 2 (cogdl/models/emb/line.py), on an edge table that is already on the device.  The
+ * law -- draws, order of updates, every rounding -- is csrc/line_law.h on top of csrc/sgns_law.h.  Host twin:
+ * cogdl_host_line_train.  cogdl_hip_sgns_init serves initialisation (emb from the seed, ctx = 0).
+ *   eu, ev       int64 [M], M >= 1: the endpoints of the undirected edges, ids in [0, V).  A sample draws an edge in
+ *                proportion to its weight and orients it by a fair coin.
+ *   ecum         NULL (unit weights), or int64 [M]: cumulative weights, non-decreasing, first entry >= 0, last entry in
+ *                [1, 2^52] (callers build 2^52).  An edge of weight 0 is never drawn.
+ *   ncum         uint32 [V]: cumulative node noise table, non-decreasing, last entry >= 1 (callers build 2^31 - 1).
+ *   exp_table    float [1000], as for cogdl_hip_sgns_train.
+ *   D, negative  1..512, 1..16.  order 1: targets are rows of emb, ctx is not used (may be NULL).  order 2: rows of ctx.
+ *   S            >= 0 samples; sample s runs at the learning rate alpha * max(1 - s / S, 1e-4).  alpha > 0.
+ *   emb, ctx     float [V, D] row-major, read and updated in place.
+ *   workers      1: one launch of one wave, samples in order; the result equals the host twin's bit for bit.  Slow by
+ *                construction.  Anything else: launches of at most samples_in_flight consecutive samples (0 = the library's
+ *                default) in sample order; the samples of one launch run concurrently and update the tables without locks
+ *                (no-return float atomics: no add is lost), so results differ from run to run.
+ *   *flags       device int, zeroed by the call, then set by a validation pass that runs before any update: 1 an endpoint
+ *                outside [0, V), 2 a malformed ncum, 4 a malformed ecum.  Non-zero: the tables were not touched.  Nothing is
+ *                read out of bounds.
+ *   Stream-ordered, allocates nothing, does not synchronise.
+ * ------------------------------------------------------------------------------------------------------------------- */
+COGDL_API int cogdl_hip_line_train(const int64_t *eu, const int64_t *ev, const int64_t *ecum, int64_t M, int64_t V,
+                       const uint32_t *ncum, const float *exp_table, int D, int negative, int order, int64_t S, double alpha,
+                       uint64_t seed, int workers, int64_t samples_in_flight, float *emb, float *ctx, int *flags,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

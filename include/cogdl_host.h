@@ -239,6 +239,18 @@ COGDL_HOST_API int cogdl_host_kg_train_batch(const int32_t *triples, const float
                                              uint64_t seed, uint32_t tag, uint64_t first_sid, int index64, int64_t *positive,
                                              void *negative, float *weight, int *status);
 
+/* Edge-sampled skip-gram training (LINE, orders 1 and 2); the host twin of cogdl_hip_line_train (include/cogdl_hip.h, where
+ * the contract is spelled out): same arguments minus samples_in_flight and the stream, all pointers host memory.
+ * workers == 1 is strictly sequential and returns EXACTLY the tables of the GPU's serial mode (both run csrc/line_law.h);
+ * workers == 0 (OpenMP's default thread count) or > 1 runs the samples in parallel without locks.
+ * trace: NULL, or double [trace_cap, 5] filled in the sequential mode only (COGDL_HOST_EINVAL otherwise) with one record
+ * (sample, input id u, target id, label, learning rate) per applied target, in order; *trace_n receives the number of
+ * applied targets, which may exceed trace_cap (the surplus is not written). */
+COGDL_HOST_API int cogdl_host_line_train(const int64_t *eu, const int64_t *ev, const int64_t *ecum, int64_t M, int64_t V,
+                                         const uint32_t *ncum, const float *exp_table, int D, int negative, int order,
+                                         int64_t S, double alpha, uint64_t seed, int workers, float *emb, float *ctx,
+                                         int *flags, double *trace, int64_t trace_cap, int64_t *trace_n);
+
 #ifdef __cplusplus
 }
 #endif
