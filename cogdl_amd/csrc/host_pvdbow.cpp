@@ -1,12 +1,14 @@
 // host_pvdbow.cpp -- the host twin of csrc/pvdbow.hip: PV-DBOW training over ragged documents.  The draws, the order of the
 // updates and every rounding are pvdbow_law.h's (on top of sgns_law.h), so with workers == 1 (strictly sequential) the two
 // tables equal the GPU's serial mode bit for bit.  workers != 1 runs the documents of an epoch under OpenMP without locks
-// (Hogwild on syn1; a dv row has one writer): fast, not reproducible.  No HIP.
+// (Hogwild on syn1; a dv row has one writer): fast, not reproducible.  The target step and the loop over documents are
+// sgns_host.h's, the host side of the wave-level step whose memory rules csrc/sgns_step.h states.  No HIP.
 #include <cstdint>
 #include <vector>
 
 #include "../../include/cogdl_host.h"
 #include "pvdbow_law.h"
+#include "sgns_host.h"
 
 namespace {
 namespace sg = cogdl_sgns;
@@ -25,19 +27,8 @@ struct Job {
     int B;  // butterfly width
 };
 
-// the dot product in sgns_law.h's order: lane sums over d % 64, then the butterfly's lower half
-inline float dot(const float *__restrict__ a, const float *__restrict__ b, int D, int B) {
-    float p[sg::kLanes];
-    const int m = D < sg::kLanes ? D : sg::kLanes;
-    for (int l = 0; l < m; ++l) p[l] = 0.0f + a[l] * b[l];
-    for (int l = m; l < B; ++l) p[l] = 0.0f;
-    for (int d = sg::kLanes; d < D; ++d) p[d & (sg::kLanes - 1)] = p[d & (sg::kLanes - 1)] + a[d] * b[d];
-    for (int s = B >> 1; s > 0; s >>= 1)
-        for (int l = 0; l < s; ++l) p[l] = p[l] + p[l + s];
-    return p[0];
-}
-
-void train_doc(const Job &J, int64_t e, int64_t g, float *__restrict__ neu) {
+void train_doc(const Job &J, int64_t e, int64_t g, std::vector<float> &scratch) {
+    float *__restrict__ neu = scratch.data();
     const float lr = sg::learning_rate(J.alpha, J.min_alpha, e, g, J.G, J.epochs);
     const int64_t beg = J.doc_ptr[g], end = J.doc_ptr[g + 1];
     const int D = J.D;
@@ -54,14 +45,7 @@ void train_doc(const Job &J, int64_t e, int64_t g, float *__restrict__ neu) {
                 t = pv::draw_negative(J.seed, g, e, pos, k, J.cum, J.V);
                 if (t == word) continue;
             }
-            float *__restrict__ y = J.syn1 + t * D;
-            const float f = dot(x, y, D, J.B);
-            if (!sg::applies(f)) continue;
-            const float gr = sg::gradient(f, k == 0 ? 1.0f : 0.0f, lr, J.exp_table);
-            for (int d = 0; d < D; ++d) {
-                neu[d] = neu[d] + gr * y[d];
-                y[d] = y[d] + gr * x[d];
-            }
+            sg::apply_target<sg::Skip>(x, J.syn1 + t * D, neu, D, J.B, k == 0 ? 1.0f : 0.0f, lr, J.exp_table);
         }
         for (int d = 0; d < D; ++d) x[d] = x[d] + neu[d];
     }
@@ -87,9 +71,7 @@ int cogdl_host_pvdbow_train(const int64_t *doc_ptr, int64_t G, const int64_t *wo
     if (rc) return rc == 1 ? COGDL_HOST_EINVAL : COGDL_HOST_ERANGE;
     if (!doc_ptr || !keep || !cum || !exp_table || !syn1 || !flags || (G > 0 && !dv) || (T > 0 && !words) || workers < 0)
         return COGDL_HOST_EINVAL;
-    int bad = 0;
-    for (int64_t v = 1; v < V; ++v) bad |= cum[v] < cum[v - 1] ? pv::kBadTable : 0;
-    bad |= cum[V - 1] == 0 ? pv::kBadTable : 0;
+    int bad = sg::noise_table_flags(cum, V, 0, 1, pv::kBadTable);
 #pragma omp parallel for schedule(static) reduction(| : bad) if (T >= 65536)
     for (int64_t k = 0; k < T; ++k) bad |= words[k] >= V ? pv::kBadId : 0;
     for (int64_t g = 0; g <= G; ++g) {
@@ -101,29 +83,10 @@ int cogdl_host_pvdbow_train(const int64_t *doc_ptr, int64_t G, const int64_t *wo
     if (bad || G == 0) return COGDL_HOST_OK;  // (nothing was touched)
     const Job J = {doc_ptr, words, G, T, V, D, negative, epochs, alpha, min_alpha, keep, cum, exp_table, seed, dv, syn1,
                    sg::butterfly_width(D)};
-    if (workers == 1) {
-        std::vector<float> neu((size_t)D);
-        for (int64_t e = 0; e < epochs; ++e)
-            for (int64_t g = 0; g < G; ++g) train_doc(J, e, g, neu.data());
-        return COGDL_HOST_OK;
-    }
-    for (int64_t e = 0; e < epochs; ++e) {
-        if (workers > 1) {
-#pragma omp parallel num_threads(workers)
-            {
-                std::vector<float> neu((size_t)D);
-#pragma omp for schedule(dynamic, 16)
-                for (int64_t g = 0; g < G; ++g) train_doc(J, e, g, neu.data());
-            }
-        } else {
-#pragma omp parallel
-            {
-                std::vector<float> neu((size_t)D);
-#pragma omp for schedule(dynamic, 16)
-                for (int64_t g = 0; g < G; ++g) train_doc(J, e, g, neu.data());
-            }
-        }
-    }
+    for (int64_t e = 0; e < epochs; ++e)
+        sg::parallel_for(
+            workers, G, 16, [&] { return std::vector<float>((size_t)D); },
+            [&](int64_t g, std::vector<float> &neu) { train_doc(J, e, g, neu); });
     return COGDL_HOST_OK;
 }
 

@@ -1,12 +1,13 @@
 // host_sgns.cpp -- the host twin of csrc/sgns.hip: skip-gram training with negative sampling over rows of token ids.  The
 // draws, the order of the updates and every rounding are sgns_law.h's, so with workers == 1 (strictly sequential) the two
 // tables equal the GPU's serial mode bit for bit.  workers != 1 runs the rows of an epoch under OpenMP without locks
-// (Hogwild): fast, not reproducible.  No HIP.
+// (Hogwild): fast, not reproducible.  The target step, the trace and the loop over rows are sgns_host.h's, the host side of
+// the wave-level step whose memory rules csrc/sgns_step.h states (they concern the GPU alone).  No HIP.
 #include <cstdint>
 #include <vector>
 
 #include "../../include/cogdl_host.h"
-#include "sgns_law.h"
+#include "sgns_host.h"
 
 namespace {
 namespace sg = cogdl_sgns;
@@ -24,24 +25,14 @@ struct Job {
     int B;  // butterfly width
 };
 
-struct Trace {
-    double *rec;
-    int64_t cap, n;
+struct Scratch {
+    std::vector<int32_t> s;  // the kept tokens of the row
+    std::vector<float> neu;
 };
 
-// the dot product in the header's order: lane sums over d % 64, then the butterfly's lower half
-inline float dot(const float *__restrict__ a, const float *__restrict__ b, int D, int B) {
-    float p[sg::kLanes];
-    const int m = D < sg::kLanes ? D : sg::kLanes;
-    for (int l = 0; l < m; ++l) p[l] = 0.0f + a[l] * b[l];
-    for (int l = m; l < B; ++l) p[l] = 0.0f;
-    for (int d = sg::kLanes; d < D; ++d) p[d & (sg::kLanes - 1)] = p[d & (sg::kLanes - 1)] + a[d] * b[d];
-    for (int s = B >> 1; s > 0; s >>= 1)
-        for (int l = 0; l < s; ++l) p[l] = p[l] + p[l + s];
-    return p[0];
-}
-
-void train_row(const Job &J, int64_t e, int64_t w, int32_t *s, float *__restrict__ neu, Trace *trace) {
+void train_row(const Job &J, int64_t e, int64_t w, Scratch &scratch, sg::Trace &trace) {
+    int32_t *s = scratch.s.data();
+    float *__restrict__ neu = scratch.neu.data();
     const float lr = sg::learning_rate(J.alpha, J.min_alpha, e, w, J.W, J.epochs);
     int n = 0;
     for (int p = 0; p < (int)J.L; ++p) {
@@ -65,22 +56,9 @@ void train_row(const Job &J, int64_t e, int64_t w, int32_t *s, float *__restrict
                     t = sg::draw_negative(J.seed, w, e, i, j, k, J.cum, J.V);
                     if (t == centre) continue;
                 }
-                float *__restrict__ y = J.syn1 + t * D;
-                const float f = dot(x, y, D, J.B);
-                if (!sg::applies(f)) continue;
                 const float label = k == 0 ? 1.0f : 0.0f;
-                const float g = sg::gradient(f, label, lr, J.exp_table);
-                for (int d = 0; d < D; ++d) {
-                    neu[d] = neu[d] + g * y[d];
-                    y[d] = y[d] + g * x[d];
-                }
-                if (trace) {
-                    if (trace->n < trace->cap) {
-                        double *r = trace->rec + trace->n * 6;
-                        r[0] = (double)e, r[1] = (double)w, r[2] = (double)in, r[3] = (double)t, r[4] = (double)label, r[5] = (double)lr;
-                    }
-                    ++trace->n;
-                }
+                if (sg::apply_target<sg::Skip>(x, J.syn1 + t * D, neu, D, J.B, label, lr, J.exp_table))
+                    trace.add(e, w, in, t, label, lr);
             }
             for (int d = 0; d < D; ++d) x[d] = x[d] + neu[d];
         }
@@ -111,43 +89,19 @@ int cogdl_host_sgns_train(const int64_t *walks, int64_t W, int64_t L, int64_t V,
     if (!keep || !cum || !exp_table || !syn0 || !syn1 || !flags || (W > 0 && !walks) || workers < 0) return COGDL_HOST_EINVAL;
     if (trace && (trace_cap < 0 || !trace_n || workers != 1)) return COGDL_HOST_EINVAL;
     if (trace_n) *trace_n = 0;
-    int bad = 0;
-    for (int64_t v = 1; v < V; ++v) bad |= cum[v] < cum[v - 1] ? sg::kBadTable : 0;
-    bad |= cum[V - 1] == 0 ? sg::kBadTable : 0;
+    int bad = sg::noise_table_flags(cum, V, 0, 1, sg::kBadTable);
 #pragma omp parallel for schedule(static) reduction(| : bad) if (W * L >= 65536)
     for (int64_t k = 0; k < W * L; ++k) bad |= walks[k] >= V ? sg::kBadId : 0;
     *flags = bad;
     if (bad || W == 0) return COGDL_HOST_OK;  // (nothing was touched)
     const Job J = {walks, W, L, V, D, window, negative, epochs, alpha, min_alpha, keep, cum, exp_table, seed, syn0, syn1,
                    sg::butterfly_width(D)};
-    if (workers == 1) {
-        Trace tr = {trace, trace_cap, 0};
-        std::vector<int32_t> s((size_t)L);
-        std::vector<float> neu((size_t)D);
-        for (int64_t e = 0; e < epochs; ++e)
-            for (int64_t w = 0; w < W; ++w) train_row(J, e, w, s.data(), neu.data(), trace ? &tr : nullptr);
-        if (trace_n) *trace_n = tr.n;
-        return COGDL_HOST_OK;
-    }
-    for (int64_t e = 0; e < epochs; ++e) {
-        if (workers > 1) {
-#pragma omp parallel num_threads(workers)
-            {
-                std::vector<int32_t> s((size_t)L);
-                std::vector<float> neu((size_t)D);
-#pragma omp for schedule(dynamic, 16)
-                for (int64_t w = 0; w < W; ++w) train_row(J, e, w, s.data(), neu.data(), nullptr);
-            }
-        } else {
-#pragma omp parallel
-            {
-                std::vector<int32_t> s((size_t)L);
-                std::vector<float> neu((size_t)D);
-#pragma omp for schedule(dynamic, 16)
-                for (int64_t w = 0; w < W; ++w) train_row(J, e, w, s.data(), neu.data(), nullptr);
-            }
-        }
-    }
+    sg::Trace tr = {trace, trace_cap, 0};
+    for (int64_t e = 0; e < epochs; ++e)
+        sg::parallel_for(
+            workers, W, 16, [&] { return Scratch{std::vector<int32_t>((size_t)L), std::vector<float>((size_t)D)}; },
+            [&](int64_t w, Scratch &scratch) { train_row(J, e, w, scratch, tr); });
+    if (trace_n) *trace_n = tr.n;
     return COGDL_HOST_OK;
 }
 

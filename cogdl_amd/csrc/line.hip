@@ -19,17 +19,16 @@
 //   workers != 1   launches of at most samples_in_flight consecutive samples, in sample order.  The samples of one launch run
 //                  concurrently and update the tables without locks (Hogwild); within a sample the law holds.
 //
-// Coherence.  The rules of sgns.hip ("Coherence") hold here unchanged: every load of a table row is an agent-scope atomic
-// load (it bypasses the CU's vector L1), every row update is a no-return atomicAdd(float) executed at the memory side (no add
-// is ever lost), the wave waits for its own updates (s_waitcnt vmcnt(0)) before it re-reads a row it has updated inside the
-// sample, and what ANOTHER XCD added to a row can stay invisible in this XCD's L2 at most until the launch ends: the kernel
-// boundary bounds the staleness, which is why samples go in launches of samples_in_flight and not in one persistent grid.
+// Coherence.  Table rows are read and updated through sgns_step.h, under the rules stated at its head ("Coherence"), with the
+// memory-side atomic add as the only row update.  This kernel keeps its own loop over the targets (unrolled, with prefetch
+// slots and the skip / repeat masks) and so its own wait before the re-read of a repeated target; samples go in launches of
+// samples_in_flight and not in one persistent grid because the kernel boundary bounds how stale another XCD's copy can be.
 // Error flags are raised by a validation pass that runs first in the stream; the training kernels read the word and leave
 // the tables untouched when it is non-zero.  Ids are bounds-checked again where they are used: nothing is read out of bounds.
 #include "common.h"
 
 #include "line_law.h"
-#include "sgns_mem.h"
+#include "sgns_step.h"
 
 namespace cogdl {
 
@@ -62,9 +61,7 @@ template <int KD, bool PREFETCH, bool ORDERED>
 __global__ __launch_bounds__(kLineBlock, 4) void line_train_kernel(LineJob J, int64_t s0, int64_t n, int64_t per) {
     __shared__ float exp_lds[cogdl_sgns::kExpTable];
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    for (int k = threadIdx.x; k < cogdl_sgns::kExpTable; k += blockDim.x) exp_lds[k] = J.exp_table[k];
-    __syncthreads();
-    if (*(const volatile int *)J.flags != 0) return;  // the validation pass found a bad id or table: touch nothing
+    if (!stage_exp_table(exp_lds, J.exp_table, J.flags)) return;  // a bad id or table: touch nothing
     const int D = J.D, K = J.K, B = cogdl_sgns::butterfly_width(D);
     const int64_t w = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
     const int64_t first = s0 + w * per, stop = s0 + n;
@@ -131,21 +128,15 @@ __global__ __launch_bounds__(kLineBlock, 4) void line_train_kernel(LineJob J, in
             const uint32_t skip = (uint32_t)__builtin_amdgcn_readlane((int)skip_l, i);
             const uint32_t dup = (uint32_t)__builtin_amdgcn_readlane((int)dup_l, i);
             float *xrow = J.emb + (int64_t)u * D + lane;
-            float x[KD], err[KD];
-#pragma unroll
-            for (int q = 0; q < KD; ++q) {
-                x[q] = lane + q * kWave < D ? row_load(xrow + q * kWave) : 0.0f;
-                err[q] = 0.0f;
-            }
+            float x[KD], err[KD] = {};
+            load_row<KD>(x, xrow, lane, D);
             float y[PREFETCH ? kLineTargets : 1][KD];
             if constexpr (PREFETCH) {
 #pragma unroll
                 for (int k = 0; k < kLineTargets; ++k)
                     if (k <= K && !(((skip | dup) >> k) & 1u)) {
                         const int32_t t = k == 0 ? v : __builtin_amdgcn_readlane(neg[k == 0 ? 0 : k - 1], i);
-                        const float *yrow = J.tgt + (int64_t)t * D + lane;
-#pragma unroll
-                        for (int q = 0; q < KD; ++q) y[k][q] = lane + q * kWave < D ? row_load(yrow + q * kWave) : 0.0f;
+                        load_row<KD>(y[k], J.tgt + (int64_t)t * D + lane, lane, D);
                     }
             }
 #pragma unroll
@@ -157,25 +148,10 @@ __global__ __launch_bounds__(kLineBlock, 4) void line_train_kernel(LineJob J, in
                 const bool again = (dup >> k) & 1u;
                 if (!PREFETCH || again) {
                     if (again) wait_own_updates();  // a target this sample has already updated
-#pragma unroll
-                    for (int q = 0; q < KD; ++q) y[slot][q] = lane + q * kWave < D ? row_load(yrow + q * kWave) : 0.0f;
+                    load_row<KD>(y[slot], yrow, lane, D);
                 }
-                float p = 0.0f;
-#pragma unroll
-                for (int q = 0; q < KD; ++q)
-                    if (lane + q * kWave < D) p = p + x[q] * y[slot][q];
-#pragma unroll
-                for (int sft = kWave / 2; sft > 0; sft >>= 1)
-                    if (sft < B) p = p + __shfl_xor(p, sft, kWave);
-                const float f = uniform_f32(p);
-                if (!ln::applies(f)) continue;
-                const float g = ln::gradient(f, k == 0 ? 1.0f : 0.0f, lr, exp_lds);
-#pragma unroll
-                for (int q = 0; q < KD; ++q)
-                    if (lane + q * kWave < D) {
-                        err[q] = err[q] + g * y[slot][q];
-                        row_add<false>(yrow + q * kWave, y[slot][q], g * x[q]);
-                    }
+                const float f = wave_dot<KD>(x, y[slot], lane, D, B);
+                update_target<KD, ln::Saturate, false>(f, x, y[slot], yrow, err, k == 0 ? 1.0f : 0.0f, lr, exp_lds, lane, D);
             }
 #pragma unroll
             for (int q = 0; q < KD; ++q)
@@ -187,8 +163,8 @@ __global__ __launch_bounds__(kLineBlock, 4) void line_train_kernel(LineJob J, in
 
 __global__ void line_check_kernel(const int64_t *__restrict__ eu, const int64_t *__restrict__ ev, const int64_t *__restrict__ ecum,
                                   int64_t M, const uint32_t *__restrict__ ncum, int64_t V, int *__restrict__ flags) {
-    int err = 0;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x, first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int err = cogdl_sgns::noise_table_flags(ncum, V, first, stride, ln::kBadNodeTable);
     for (int64_t k = first; k < M; k += stride) {
         if ((uint64_t)eu[k] >= (uint64_t)V || (uint64_t)ev[k] >= (uint64_t)V) err |= ln::kBadEndpoint;
         if (ecum) {
@@ -197,26 +173,16 @@ __global__ void line_check_kernel(const int64_t *__restrict__ eu, const int64_t 
             if (k == M - 1 && (ecum[k] < 1 || ecum[k] > ln::kEdgeTotalMax)) err |= ln::kBadEdgeTable;
         }
     }
-    for (int64_t v = first; v < V; v += stride) {
-        if (v > 0 && ncum[v] < ncum[v - 1]) err |= ln::kBadNodeTable;
-        if (v == V - 1 && ncum[v] == 0) err |= ln::kBadNodeTable;
-    }
     raise_flags(flags, err);
 }
 
-template <int KD, bool PREFETCH>
+// PREFETCH up to D = 64 (one element per lane)
 static void line_launch(bool ordered, unsigned blocks, unsigned threads, hipStream_t s, const LineJob &J, int64_t s0, int64_t n,
                         int64_t per) {
-    if (ordered) hipLaunchKernelGGL((line_train_kernel<KD, PREFETCH, true>), dim3(blocks), dim3(threads), 0, s, J, s0, n, per);
-    else hipLaunchKernelGGL((line_train_kernel<KD, PREFETCH, false>), dim3(blocks), dim3(threads), 0, s, J, s0, n, per);
-}
-
-static void line_launch_any(int D, bool ordered, unsigned blocks, unsigned threads, hipStream_t s, const LineJob &J, int64_t s0,
-                            int64_t n, int64_t per) {
-    if (D <= 64) line_launch<1, true>(ordered, blocks, threads, s, J, s0, n, per);
-    else if (D <= 128) line_launch<2, false>(ordered, blocks, threads, s, J, s0, n, per);
-    else if (D <= 256) line_launch<4, false>(ordered, blocks, threads, s, J, s0, n, per);
-    else line_launch<8, false>(ordered, blocks, threads, s, J, s0, n, per);
+    with_row_width(J.D, ordered, [&](auto kd, auto ord) {
+        constexpr int KD = decltype(kd)::value;
+        hipLaunchKernelGGL((line_train_kernel<KD, KD == 1, decltype(ord)::value>), dim3(blocks), dim3(threads), 0, s, J, s0, n, per);
+    });
 }
 
 }  // namespace cogdl
@@ -241,16 +207,11 @@ extern "C" int cogdl_hip_line_train(const int64_t *eu, const int64_t *ev, const 
     if (st != COGDL_HIP_OK || S == 0) return st;
     const LineJob J = {eu, ev, ecum, M, V, ncum, exp_table, D, negative, S, alpha, seed, emb, order == 1 ? emb : ctx, flags};
     if (workers == 1) {  // one wave, every sample in order
-        line_launch_any(D, true, 1u, (unsigned)kWave, s, J, 0, S, S);
+        line_launch(true, 1u, (unsigned)kWave, s, J, 0, S, S);
         return launch_status();
     }
-    const int64_t chunk = samples_in_flight > 0 ? samples_in_flight : kLineSamplesInFlight;
-    for (int64_t s0 = 0; s0 < S; s0 += chunk) {
-        const int64_t n = std::min<int64_t>(chunk, S - s0);
+    return launch_chunks(S, samples_in_flight > 0 ? samples_in_flight : kLineSamplesInFlight, [&](int64_t s0, int64_t n) {
         const int64_t per = (n + kLineMaxWaves - 1) / kLineMaxWaves, waves = (n + per - 1) / per;
-        line_launch_any(D, false, (unsigned)((waves + kLineWaves - 1) / kLineWaves), (unsigned)kLineBlock, s, J, s0, n, per);
-        st = launch_status();
-        if (st != COGDL_HIP_OK) return st;
-    }
-    return COGDL_HIP_OK;
+        line_launch(false, (unsigned)((waves + kLineWaves - 1) / kLineWaves), (unsigned)kLineBlock, s, J, s0, n, per);
+    });
 }

@@ -58,14 +58,7 @@ COGDL_WALK_FN int64_t draw_edge(uint64_t seed, int64_t s, const int64_t *ecum, i
     swapped = (d.z & 1u) != 0;
     const uint64_t x64 = ((uint64_t)d.y << 32) | d.x;
     if (!ecum) return (int64_t)cogdl_walk::mulhi64(x64, (uint64_t)M);
-    const int64_t r = (int64_t)cogdl_walk::mulhi64(x64, (uint64_t)ecum[M - 1]);
-    int64_t lo = 0, hi = M - 1;
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (ecum[mid] > r) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
+    return cogdl_sgns::first_above(ecum, M, (int64_t)cogdl_walk::mulhi64(x64, (uint64_t)ecum[M - 1]));
 }
 
 // what negative d in 1..K of sample s looks up in ncum
@@ -73,16 +66,9 @@ COGDL_WALK_FN uint32_t negative_key(uint64_t seed, int64_t s, int d, const uint3
     return draw(seed, s, (uint32_t)d).x % ncum[V - 1];
 }
 
-// the first index with ncum[t] > r; stays inside [0, V - 1] whatever ncum holds
+// the first index with ncum[t] > the key
 COGDL_WALK_FN int64_t draw_negative(uint64_t seed, int64_t s, int d, const uint32_t *ncum, int64_t V) {
-    const uint32_t r = negative_key(seed, s, d, ncum, V);
-    int64_t lo = 0, hi = V - 1;
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (ncum[mid] > r) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
+    return cogdl_sgns::first_above(ncum, V, negative_key(seed, s, d, ncum, V));
 }
 
 COGDL_WALK_FN float learning_rate(double alpha, int64_t s, int64_t S) {
@@ -90,19 +76,21 @@ COGDL_WALK_FN float learning_rate(double alpha, int64_t s, int64_t S) {
     return (float)(alpha * (left > 1e-4 ? left : 1e-4));
 }
 
-COGDL_WALK_FN bool applies(float f) { return f == f; }  // only a NaN skips the target
-
-COGDL_WALK_FN float gradient(float f, float label, float lr, const float *exp_table) {
-    float sig;
-    if (f >= 6.0f) sig = 1.0f;
-    else if (f <= -6.0f) sig = 0.0f;
-    else {
-        int idx = (int)((f + 6.0f) * (1000.0f / 12.0f));
-        idx = idx > cogdl_sgns::kExpTable - 1 ? cogdl_sgns::kExpTable - 1 : idx;
-        sig = exp_table[idx];
+// LINE's rule for sgns_law.h's inner step: only a NaN skips the target; outside -6 < f < 6 the sigmoid saturates
+struct Saturate {
+    static COGDL_WALK_FN bool applies(float f) { return f == f; }
+    static COGDL_WALK_FN float gradient(float f, float label, float lr, const float *exp_table) {
+        float sig;
+        if (f >= 6.0f) sig = 1.0f;
+        else if (f <= -6.0f) sig = 0.0f;
+        else {
+            int idx = (int)((f + 6.0f) * (1000.0f / 12.0f));
+            idx = idx > cogdl_sgns::kExpTable - 1 ? cogdl_sgns::kExpTable - 1 : idx;
+            sig = exp_table[idx];
+        }
+        return (label - sig) * lr;
     }
-    return (label - sig) * lr;
-}
+};
 
 // argument checks both entry points share (0 = fine, 1 = invalid, 2 = out of range)
 inline int args_status(int64_t M, int64_t V, int D, int negative, int order, int64_t S, double alpha) {

@@ -4,9 +4,9 @@
 // includes both.
 //
 // Shape.  One wave64 per document.  dv[g] belongs to its wave alone: lane l keeps the elements d = l, l + 64, .. (at most 8)
-// in VGPRs for the whole document and stores them once at its end.  Only syn1 rows are shared between waves, and the
-// coherence rules of sgns.hip apply to them: agent-scope loads, the update variant of kTuneSgnsVariant, and the wave waits
-// for its own updates at the end of every position and before it re-reads a target row it has already updated inside one.
+// in VGPRs for the whole document and stores them once at its end.  Only syn1 rows are shared between waves; they are read
+// and updated by the wave-level step of sgns_step.h, under the rules stated at its head ("Coherence"), with the update
+// variant of kTuneSgnsVariant, and the wave waits for its own updates at the end of every position.
 // Token ids are read 64 at a time, `keep` is decided per lane and the kept positions are walked off a ballot in ascending
 // order; lanes 1..K draw and binary-search the K negatives of a position in parallel.
 //
@@ -21,7 +21,7 @@
 #include "common.h"
 
 #include "pvdbow_law.h"
-#include "sgns_mem.h"
+#include "sgns_step.h"
 
 namespace cogdl {
 
@@ -50,9 +50,7 @@ template <int KD, bool STORES>
 __global__ __launch_bounds__(kPvBlock) void pvdbow_train_kernel(PvJob J, int64_t doc0, int64_t n_docs, int64_t e0, int64_t e1) {
     __shared__ float exp_lds[sg::kExpTable];
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    for (int k = threadIdx.x; k < sg::kExpTable; k += blockDim.x) exp_lds[k] = J.exp_table[k];
-    __syncthreads();
-    if (*(const volatile int *)J.flags != 0) return;  // the validation pass found a bad id, table or doc_ptr: touch nothing
+    if (!stage_exp_table(exp_lds, J.exp_table, J.flags)) return;  // a bad id, table or doc_ptr: touch nothing
     const int D = J.D, B = sg::butterfly_width(D);
     const int64_t n_waves = (int64_t)gridDim.x * (blockDim.x >> 6);
     for (int64_t e = e0; e < e1; ++e) {
@@ -62,8 +60,7 @@ __global__ __launch_bounds__(kPvBlock) void pvdbow_train_kernel(PvJob J, int64_t
             if (beg >= end) continue;
             float *xrow = J.dv + g * D + lane;
             float x[KD];
-#pragma unroll
-            for (int k = 0; k < KD; ++k) x[k] = lane + k * kWave < D ? row_load(xrow + k * kWave) : 0.0f;
+            load_row<KD>(x, xrow, lane, D);
             for (int64_t p0 = beg; p0 < end; p0 += kWave) {
                 const int64_t q = p0 + lane;
                 int64_t id = -1;
@@ -84,34 +81,8 @@ __global__ __launch_bounds__(kPvBlock) void pvdbow_train_kernel(PvJob J, int64_t
                         tl = (int32_t)pv::draw_negative(J.seed, g, e, pos, lane, J.cum, J.V);
                         if (tl == word) tl = -1;
                     }
-                    float neu[KD];
-#pragma unroll
-                    for (int k = 0; k < KD; ++k) neu[k] = 0.0f;
-                    for (int k = 0; k <= J.K; ++k) {
-                        const int32_t t = __builtin_amdgcn_readlane(tl, k);
-                        if (t < 0) continue;
-                        if (__any(lane < k && tl == t)) wait_own_updates();  // a target this position has already updated
-                        float *yrow = J.syn1 + (int64_t)t * D + lane;
-                        float y[KD];
-#pragma unroll
-                        for (int c = 0; c < KD; ++c) y[c] = lane + c * kWave < D ? row_load(yrow + c * kWave) : 0.0f;
-                        float p = 0.0f;
-#pragma unroll
-                        for (int c = 0; c < KD; ++c)
-                            if (lane + c * kWave < D) p = p + x[c] * y[c];
-#pragma unroll
-                        for (int sft = kWave / 2; sft > 0; sft >>= 1)
-                            if (sft < B) p = p + __shfl_xor(p, sft, kWave);
-                        const float f = uniform_f32(p);
-                        if (!sg::applies(f)) continue;
-                        const float gr = sg::gradient(f, k == 0 ? 1.0f : 0.0f, lr, exp_lds);
-#pragma unroll
-                        for (int c = 0; c < KD; ++c)
-                            if (lane + c * kWave < D) {
-                                neu[c] = neu[c] + gr * y[c];
-                                row_add<STORES>(yrow + c * kWave, y[c], gr * x[c]);
-                            }
-                    }
+                    float neu[KD] = {};
+                    update_lane_targets<KD, sg::Skip, STORES>(tl, J.K, x, neu, J.syn1, lr, exp_lds, lane, D, B);
 #pragma unroll
                     for (int c = 0; c < KD; ++c) x[c] = x[c] + neu[c];
                     wait_own_updates();
@@ -127,13 +98,9 @@ __global__ __launch_bounds__(kPvBlock) void pvdbow_train_kernel(PvJob J, int64_t
 
 __global__ void pvdbow_check_kernel(const int64_t *__restrict__ doc_ptr, int64_t G, const int64_t *__restrict__ words, int64_t T,
                                     const uint32_t *__restrict__ cum, int64_t V, int *__restrict__ flags) {
-    int err = 0;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x, first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int err = sg::noise_table_flags(cum, V, first, stride, pv::kBadTable);
     for (int64_t k = first; k < T; k += stride) err |= words[k] >= V ? pv::kBadId : 0;
-    for (int64_t v = first; v < V; v += stride) {
-        if (v > 0 && cum[v] < cum[v - 1]) err |= pv::kBadTable;
-        if (v == V - 1 && cum[v] == 0) err |= pv::kBadTable;
-    }
     for (int64_t g = first; g <= G; g += stride) {
         const int64_t a = doc_ptr[g];
         if (a < 0 || a > T) err |= pv::kBadPtr;
@@ -148,19 +115,12 @@ __global__ void pvdbow_init_kernel(float *__restrict__ dv, int64_t G, float *__r
     for (int64_t k = first; k < V * D; k += stride) syn1[k] = 0.0f;
 }
 
-template <int KD>
-static void pvdbow_launch(bool stores, unsigned blocks, unsigned threads, hipStream_t s, const PvJob &J, int64_t doc0, int64_t n_docs,
-                          int64_t e0, int64_t e1) {
-    if (stores) hipLaunchKernelGGL((pvdbow_train_kernel<KD, true>), dim3(blocks), dim3(threads), 0, s, J, doc0, n_docs, e0, e1);
-    else hipLaunchKernelGGL((pvdbow_train_kernel<KD, false>), dim3(blocks), dim3(threads), 0, s, J, doc0, n_docs, e0, e1);
-}
-
-static void pvdbow_launch_any(int D, bool stores, unsigned blocks, unsigned threads, hipStream_t s, const PvJob &J, int64_t doc0,
-                              int64_t n_docs, int64_t e0, int64_t e1) {
-    if (D <= 64) pvdbow_launch<1>(stores, blocks, threads, s, J, doc0, n_docs, e0, e1);
-    else if (D <= 128) pvdbow_launch<2>(stores, blocks, threads, s, J, doc0, n_docs, e0, e1);
-    else if (D <= 256) pvdbow_launch<4>(stores, blocks, threads, s, J, doc0, n_docs, e0, e1);
-    else pvdbow_launch<8>(stores, blocks, threads, s, J, doc0, n_docs, e0, e1);
+static void pvdbow_launch(unsigned blocks, unsigned threads, hipStream_t s, const PvJob &J, int64_t doc0, int64_t n_docs, int64_t e0,
+                          int64_t e1) {
+    with_row_width(J.D, g_tuning[kTuneSgnsVariant] == 1, [&](auto kd, auto stores) {
+        hipLaunchKernelGGL((pvdbow_train_kernel<decltype(kd)::value, decltype(stores)::value>), dim3(blocks), dim3(threads), 0, s, J,
+                           doc0, n_docs, e0, e1);
+    });
 }
 
 }  // namespace cogdl
@@ -194,18 +154,14 @@ extern "C" int cogdl_hip_pvdbow_train(const int64_t *doc_ptr, int64_t G, const i
     int st = launch_status();
     if (st != COGDL_HIP_OK || G == 0) return st;
     const PvJob J = {doc_ptr, words, G, T, V, D, negative, epochs, alpha, min_alpha, keep, cum, exp_table, seed, dv, syn1, flags};
-    const bool stores = g_tuning[kTuneSgnsVariant] == 1;
     if (workers == 1) {  // one wave, every epoch and document in order
-        pvdbow_launch_any(D, stores, 1u, (unsigned)kWave, s, J, 0, G, 0, epochs);
+        pvdbow_launch(1u, (unsigned)kWave, s, J, 0, G, 0, epochs);
         return launch_status();
     }
     const int64_t chunk = docs_in_flight > 0 ? docs_in_flight : kPvDocsInFlight;
-    for (int64_t ep = 0; ep < epochs; ++ep)
-        for (int64_t doc0 = 0; doc0 < G; doc0 += chunk) {
-            const int64_t n_docs = std::min<int64_t>(chunk, G - doc0);
-            pvdbow_launch_any(D, stores, (unsigned)((n_docs + kPvWaves - 1) / kPvWaves), (unsigned)kPvBlock, s, J, doc0, n_docs, ep, ep + 1);
-            st = launch_status();
-            if (st != COGDL_HIP_OK) return st;
-        }
-    return COGDL_HIP_OK;
+    for (int64_t ep = 0; ep < epochs && st == COGDL_HIP_OK; ++ep)
+        st = launch_chunks(G, chunk, [&](int64_t doc0, int64_t n_docs) {
+            pvdbow_launch((unsigned)((n_docs + kPvWaves - 1) / kPvWaves), (unsigned)kPvBlock, s, J, doc0, n_docs, ep, ep + 1);
+        });
+    return st;
 }

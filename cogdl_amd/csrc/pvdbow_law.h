@@ -1,7 +1,7 @@
 // pvdbow_law.h -- the law of PV-DBOW training (gensim's Doc2Vec(dm=0): skip-gram with negative sampling whose input row is
 // the document's vector) over ragged documents, shared by the HIP kernel (pvdbow.hip) and its host twin (host_pvdbow.cpp).
-// On top of sgns_law.h: draw_x, draw_negative's binary search, learning_rate, applies, gradient, butterfly_width and the
-// order of the dot product are used unchanged.  There is no cap on a document's length and no window draw.
+// On top of sgns_law.h: draw_x, draw_negative's binary search, learning_rate, the Skip rule (applies, gradient),
+// butterfly_width, init_value and the order of the dot product are used unchanged.  There is no cap on a document's length and no window draw.
 //
 // Inputs.  doc_ptr int64 [G + 1], non-decreasing from 0 to at most T; words int64 [T] with ids in [0, V) (a negative id is
 // padding); D in [1, 512], negative K in [1, 16], epochs >= 1, alpha / min_alpha, keep / cum uint32 [V] and exp_table as in
@@ -44,13 +44,7 @@ COGDL_WALK_FN int64_t draw_negative(uint64_t seed, int64_t doc, int64_t epoch, u
     return sg::draw_negative(seed, doc, epoch, (int)(pos & 0xffffu), (int)(pos >> 16), d, cum, V);
 }
 
-COGDL_WALK_FN float init_value(uint64_t seed, int64_t g, int d, int D) {
-    const uint32_t u24 = cogdl_walk::philox4x32_10((uint32_t)(uint64_t)g, (uint32_t)((uint64_t)g >> 32), (uint32_t)d, kDocStream,
-                                                   (uint32_t)seed, (uint32_t)(seed >> 32))
-                             .x >>
-                         8;
-    return ((float)u24 * (1.0f / 16777216.0f) - 0.5f) / (float)D;
-}
+COGDL_WALK_FN float init_value(uint64_t seed, int64_t g, int d, int D) { return sg::init_value(seed, g, d, D, kDocStream); }
 
 // argument checks both entry points share (0 = fine, 1 = invalid, 2 = out of range)
 inline int args_status(int64_t G, int64_t T, int64_t V, int D, int negative, int64_t epochs, double alpha, double min_alpha) {

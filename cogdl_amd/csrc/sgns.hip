@@ -14,24 +14,18 @@
 //   workers != 1   per epoch, launches of at most rows_in_flight rows, in row order.  Rows of one launch run concurrently
 //                  and update the tables without locks (Hogwild); within a row the law holds.
 //
-// Coherence.  The eight XCDs' L2s are not coherent with each other and a CU's vector L1 is refreshed by nobody, so:
-//   * every load of an embedding row is an agent-scope atomic load (global_load ... sc1): it bypasses L1, where a line this
-//     wave updated a moment ago (the input row is re-read for ~2 * window consecutive centres) would still be the old one;
-//   * a row update is either a no-return atomicAdd(float) (kTuneSgnsVariant 0: executed at the memory side, no add is
-//     ever lost, the line leaves this XCD's L2) or an agent-scope atomic store of (loaded + delta) (variant 1: a
-//     write-through store; concurrent writers of one row overwrite each other as in CPU Hogwild);
-//   * the wave waits for its own updates (s_waitcnt vmcnt(0)) at the end of every pair and before it re-reads a target row
-//     it has already updated inside the pair, so its own earlier updates are in memory before the re-read is issued;
-//   * what ANOTHER XCD added to a row can stay invisible here for as long as this XCD's L2 keeps its copy, at most until
-//     the launch ends: the kernel boundary bounds the staleness, which is why rows go in launches of rows_in_flight and not
-//     in one persistent grid.
+// Coherence.  Rows of syn0 and syn1 are read and updated by the wave-level step of sgns_step.h, under the rules stated at
+// its head ("Coherence"); this kernel adds the wait for the wave's own updates at the end of every pair (the input row of a
+// pair is the input row of the next centres' pairs), takes the row-update variant from tuning key 17 (kTuneSgnsVariant), and
+// sends rows in launches of rows_in_flight, not in one persistent grid, because the kernel boundary is what bounds how
+// stale another XCD's copy of a row can be.
 // Error flags are raised by a validation pass that runs first in the stream (ids >= V, a cum that runs backwards); the
 // training kernels read the word and leave the tables untouched when it is non-zero.  Ids are bounds-checked again where
 // they are used: nothing is read out of bounds.
 #include "common.h"
 
 #include "sgns_law.h"
-#include "sgns_mem.h"
+#include "sgns_step.h"
 
 namespace cogdl {
 
@@ -54,8 +48,6 @@ struct SgnsJob {
     const int *flags;
 };
 
-// (row_load, row_add, wait_own_updates and uniform_f32 are sgns_mem.h's: pvdbow.hip follows the same rules)
-
 __device__ __forceinline__ void sgns_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -68,9 +60,7 @@ __global__ __launch_bounds__(kSgnsBlock) void sgns_train_kernel(SgnsJob J, int64
     __shared__ float exp_lds[sg::kExpTable];
     __shared__ int32_t tok_lds[kSgnsWaves][sg::kMaxLength];
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    for (int k = threadIdx.x; k < sg::kExpTable; k += blockDim.x) exp_lds[k] = J.exp_table[k];
-    __syncthreads();
-    if (*(const volatile int *)J.flags != 0) return;  // the validation pass found a bad id or table: touch nothing
+    if (!stage_exp_table(exp_lds, J.exp_table, J.flags)) return;  // a bad id or table: touch nothing
     int32_t *s = tok_lds[wave];
     const int D = J.D, B = sg::butterfly_width(D);
     const int L = (int)J.L;
@@ -107,37 +97,9 @@ __global__ __launch_bounds__(kSgnsBlock) void sgns_train_kernel(SgnsJob J, int64
                         if (tl == centre) tl = -1;
                     }
                     float *xrow = J.syn0 + (int64_t)in * D + lane;
-                    float x[KD], neu[KD];
-#pragma unroll
-                    for (int k = 0; k < KD; ++k) {
-                        x[k] = lane + k * kWave < D ? row_load(xrow + k * kWave) : 0.0f;
-                        neu[k] = 0.0f;
-                    }
-                    for (int k = 0; k <= J.K; ++k) {
-                        const int32_t t = __builtin_amdgcn_readlane(tl, k);
-                        if (t < 0) continue;
-                        if (__any(lane < k && tl == t)) wait_own_updates();  // a target this pair has already updated
-                        float *yrow = J.syn1 + (int64_t)t * D + lane;
-                        float y[KD];
-#pragma unroll
-                        for (int q = 0; q < KD; ++q) y[q] = lane + q * kWave < D ? row_load(yrow + q * kWave) : 0.0f;
-                        float p = 0.0f;
-#pragma unroll
-                        for (int q = 0; q < KD; ++q)
-                            if (lane + q * kWave < D) p = p + x[q] * y[q];
-#pragma unroll
-                        for (int sft = kWave / 2; sft > 0; sft >>= 1)
-                            if (sft < B) p = p + __shfl_xor(p, sft, kWave);
-                        const float f = uniform_f32(p);
-                        if (!sg::applies(f)) continue;
-                        const float g = sg::gradient(f, k == 0 ? 1.0f : 0.0f, lr, exp_lds);
-#pragma unroll
-                        for (int q = 0; q < KD; ++q)
-                            if (lane + q * kWave < D) {
-                                neu[q] = neu[q] + g * y[q];
-                                row_add<STORES>(yrow + q * kWave, y[q], g * x[q]);
-                            }
-                    }
+                    float x[KD], neu[KD] = {};
+                    load_row<KD>(x, xrow, lane, D);
+                    update_lane_targets<KD, sg::Skip, STORES>(tl, J.K, x, neu, J.syn1, lr, exp_lds, lane, D, B);
 #pragma unroll
                     for (int q = 0; q < KD; ++q)
                         if (lane + q * kWave < D) row_add<STORES>(xrow + q * kWave, x[q], neu[q]);
@@ -150,13 +112,9 @@ __global__ __launch_bounds__(kSgnsBlock) void sgns_train_kernel(SgnsJob J, int64
 
 __global__ void sgns_check_kernel(const int64_t *__restrict__ walks, int64_t n_tokens, const uint32_t *__restrict__ cum, int64_t V,
                                   int *__restrict__ flags) {
-    int err = 0;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x, first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int err = sg::noise_table_flags(cum, V, first, stride, sg::kBadTable);
     for (int64_t k = first; k < n_tokens; k += stride) err |= walks[k] >= V ? sg::kBadId : 0;
-    for (int64_t v = first; v < V; v += stride) {
-        if (v > 0 && cum[v] < cum[v - 1]) err |= sg::kBadTable;
-        if (v == V - 1 && cum[v] == 0) err |= sg::kBadTable;
-    }
     raise_flags(flags, err);
 }
 
@@ -168,19 +126,12 @@ __global__ void sgns_init_kernel(float *__restrict__ syn0, float *__restrict__ s
     }
 }
 
-template <int KD>
-static void sgns_launch(bool stores, unsigned blocks, unsigned threads, hipStream_t s, const SgnsJob &J, int64_t row0, int64_t n_rows,
-                        int64_t e0, int64_t e1) {
-    if (stores) hipLaunchKernelGGL((sgns_train_kernel<KD, true>), dim3(blocks), dim3(threads), 0, s, J, row0, n_rows, e0, e1);
-    else hipLaunchKernelGGL((sgns_train_kernel<KD, false>), dim3(blocks), dim3(threads), 0, s, J, row0, n_rows, e0, e1);
-}
-
-static void sgns_launch_any(int D, bool stores, unsigned blocks, unsigned threads, hipStream_t s, const SgnsJob &J, int64_t row0,
-                            int64_t n_rows, int64_t e0, int64_t e1) {
-    if (D <= 64) sgns_launch<1>(stores, blocks, threads, s, J, row0, n_rows, e0, e1);
-    else if (D <= 128) sgns_launch<2>(stores, blocks, threads, s, J, row0, n_rows, e0, e1);
-    else if (D <= 256) sgns_launch<4>(stores, blocks, threads, s, J, row0, n_rows, e0, e1);
-    else sgns_launch<8>(stores, blocks, threads, s, J, row0, n_rows, e0, e1);
+static void sgns_launch(unsigned blocks, unsigned threads, hipStream_t s, const SgnsJob &J, int64_t row0, int64_t n_rows, int64_t e0,
+                        int64_t e1) {
+    with_row_width(J.D, g_tuning[kTuneSgnsVariant] == 1, [&](auto kd, auto stores) {
+        hipLaunchKernelGGL((sgns_train_kernel<decltype(kd)::value, decltype(stores)::value>), dim3(blocks), dim3(threads), 0, s, J, row0,
+                           n_rows, e0, e1);
+    });
 }
 
 }  // namespace cogdl
@@ -212,19 +163,14 @@ extern "C" int cogdl_hip_sgns_train(const int64_t *walks, int64_t W, int64_t L, 
     int st = launch_status();
     if (st != COGDL_HIP_OK || W == 0) return st;
     const SgnsJob J = {walks, W, L, V, D, window, negative, epochs, alpha, min_alpha, keep, cum, exp_table, seed, syn0, syn1, flags};
-    const bool stores = g_tuning[kTuneSgnsVariant] == 1;
     if (workers == 1) {  // one wave, every epoch and row in order
-        sgns_launch_any(D, stores, 1u, (unsigned)kWave, s, J, 0, W, 0, epochs);
+        sgns_launch(1u, (unsigned)kWave, s, J, 0, W, 0, epochs);
         return launch_status();
     }
     const int64_t chunk = rows_in_flight > 0 ? rows_in_flight : kSgnsRowsInFlight;
-    for (int64_t ep = 0; ep < epochs; ++ep)
-        for (int64_t row0 = 0; row0 < W; row0 += chunk) {
-            const int64_t n_rows = std::min<int64_t>(chunk, W - row0);
-            sgns_launch_any(D, stores, (unsigned)((n_rows + kSgnsWaves - 1) / kSgnsWaves), (unsigned)kSgnsBlock, s, J, row0, n_rows, ep,
-                            ep + 1);
-            st = launch_status();
-            if (st != COGDL_HIP_OK) return st;
-        }
-    return COGDL_HIP_OK;
+    for (int64_t ep = 0; ep < epochs && st == COGDL_HIP_OK; ++ep)
+        st = launch_chunks(W, chunk, [&](int64_t row0, int64_t n_rows) {
+            sgns_launch((unsigned)((n_rows + kSgnsWaves - 1) / kSgnsWaves), (unsigned)kSgnsBlock, s, J, row0, n_rows, ep, ep + 1);
+        });
+    return st;
 }

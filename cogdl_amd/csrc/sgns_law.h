@@ -58,33 +58,54 @@ COGDL_WALK_FN int window_shrink(uint64_t seed, int64_t row, int64_t epoch, int c
     return (int)(draw_x(seed, row, epoch, (uint32_t)centre, 1u) % (uint32_t)window);
 }
 
-// cum[V - 1] >= 1 is checked before any row runs; the search stays inside [0, V - 1] whatever cum holds.
-COGDL_WALK_FN int64_t draw_negative(uint64_t seed, int64_t row, int64_t epoch, int centre, int context, int d,
-                                    const uint32_t *cum, int64_t V) {
-    const uint32_t r = draw_x(seed, row, epoch, (uint32_t)centre | ((uint32_t)context << 16), 1u + (uint32_t)d) % cum[V - 1];
-    int64_t lo = 0, hi = V - 1;
+// The first index with table[index] > r, by a binary search that stays inside [0, n - 1] whatever the table holds.  Every
+// cumulative table of the trainers is searched by this one function (noise tables are uint32, LINE's edge table int64).
+template <typename T>
+COGDL_WALK_FN int64_t first_above(const T *table, int64_t n, T r) {
+    int64_t lo = 0, hi = n - 1;
     while (lo < hi) {
         const int64_t mid = lo + ((hi - lo) >> 1);
-        if (cum[mid] > r) hi = mid;
+        if (table[mid] > r) hi = mid;
         else lo = mid + 1;
     }
     return lo;
+}
+
+// cum[V - 1] >= 1 is checked before any row runs.
+COGDL_WALK_FN int64_t draw_negative(uint64_t seed, int64_t row, int64_t epoch, int centre, int context, int d,
+                                    const uint32_t *cum, int64_t V) {
+    return first_above(cum, V, draw_x(seed, row, epoch, (uint32_t)centre | ((uint32_t)context << 16), 1u + (uint32_t)d) % cum[V - 1]);
+}
+
+// `flag` if cum runs backwards or ends in 0, over the entries first, first + stride, .. that the caller walks (a thread of a
+// check kernel its own, the host all of them)
+COGDL_WALK_FN int noise_table_flags(const uint32_t *cum, int64_t V, int64_t first, int64_t stride, int flag) {
+    int err = 0;
+    for (int64_t v = first; v < V; v += stride) {
+        if (v > 0 && cum[v] < cum[v - 1]) err |= flag;
+        if (v == V - 1 && cum[v] == 0) err |= flag;
+    }
+    return err;
 }
 
 COGDL_WALK_FN float learning_rate(double alpha, double min_alpha, int64_t epoch, int64_t row, int64_t W, int64_t epochs) {
     return (float)(alpha - (alpha - min_alpha) * (double)(epoch * W + row) / (double)(epochs * W));
 }
 
-COGDL_WALK_FN bool applies(float f) { return f > -6.0f && f < 6.0f; }
+// Which targets are applied, and with what gradient: the one thing the trainers' inner step differs in.  word2vec's rule
+// (skip-gram, PV-DBOW): outside -6 < f < 6 the target is skipped (a NaN too).  LINE's rule is line_law.h's Saturate.
+struct Skip {
+    static COGDL_WALK_FN bool applies(float f) { return f > -6.0f && f < 6.0f; }
+    static COGDL_WALK_FN float gradient(float f, float label, float lr, const float *exp_table) {
+        int idx = (int)((f + 6.0f) * (1000.0f / 12.0f));
+        idx = idx > kExpTable - 1 ? kExpTable - 1 : idx;
+        return (label - exp_table[idx]) * lr;
+    }
+};
 
-COGDL_WALK_FN float gradient(float f, float label, float lr, const float *exp_table) {
-    int idx = (int)((f + 6.0f) * (1000.0f / 12.0f));
-    idx = idx > kExpTable - 1 ? kExpTable - 1 : idx;
-    return (label - exp_table[idx]) * lr;
-}
-
-COGDL_WALK_FN float init_value(uint64_t seed, int64_t v, int d, int D) {
-    const uint32_t u24 = cogdl_walk::philox4x32_10((uint32_t)(uint64_t)v, (uint32_t)((uint64_t)v >> 32), (uint32_t)d, kInitStream,
+// `stream` separates the tables that are initialised this way (pvdbow_law.h has one of its own)
+COGDL_WALK_FN float init_value(uint64_t seed, int64_t v, int d, int D, uint32_t stream = kInitStream) {
+    const uint32_t u24 = cogdl_walk::philox4x32_10((uint32_t)(uint64_t)v, (uint32_t)((uint64_t)v >> 32), (uint32_t)d, stream,
                                                    (uint32_t)seed, (uint32_t)(seed >> 32))
                              .x >>
                          8;

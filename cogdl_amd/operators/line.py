@@ -77,18 +77,15 @@ def line_train(edges, num_nodes, dim, order, samples, negative=5, alpha=0.025, e
         raise ValueError("line_train: edges must hold at least one edge")
     if num_nodes < 1 or num_nodes > 2 ** 31 - 1:
         raise ValueError("line_train: num_nodes must be in [1, 2^31) (got %d)" % num_nodes)
-    if not 1 <= dim <= MAX_DIM:
-        raise ValueError("line_train: dim must be in [1, %d] (got %d)" % (MAX_DIM, dim))
+    sgns.check_range("line_train", "dim", dim, MAX_DIM)
     if order not in (1, 2):
         raise ValueError("line_train: order must be 1 or 2 (got %d)" % order)
     if samples < 0:
         raise ValueError("line_train: samples must be >= 0 (got %d)" % samples)
-    if not 1 <= negative <= MAX_NEGATIVE:
-        raise ValueError("line_train: negative must be in [1, %d] (got %d)" % (MAX_NEGATIVE, negative))
+    sgns.check_range("line_train", "negative", negative, MAX_NEGATIVE)
     if not (np.isfinite(alpha) and alpha > 0):
         raise ValueError("line_train: alpha must be positive (got %r)" % alpha)
-    if workers < 0:
-        raise ValueError("line_train: workers must be >= 0 (got %d)" % workers)
+    sgns.check_workers("line_train", workers)
     in_flight = int(SAMPLES_IN_FLIGHT)
     if in_flight < 0:
         raise ValueError("line_train: SAMPLES_IN_FLIGHT must be >= 0 (got %d)" % in_flight)
@@ -107,9 +104,7 @@ def line_train(edges, num_nodes, dim, order, samples, negative=5, alpha=0.025, e
         init = (init,) if torch.is_tensor(init) else tuple(init)
         if len(init) != order:
             raise ValueError("line_train: init must hold %d table(s) for order %d" % (order, order))
-        for t in init:
-            if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (num_nodes, dim) or t.device != dev:
-                raise ValueError("line_train: init must be float32 [%d, %d] on %s" % (num_nodes, dim, dev))
+        sgns.check_init(init, (num_nodes,) * order, dim, dev, "line_train: init must be float32 [%d, %d] on %s" % (num_nodes, dim, dev))
     if tables is not None:
         if (len(tables) != 2 or not torch.is_tensor(tables[1]) or tables[1].dtype != torch.long or tuple(tables[1].shape) != (num_nodes,)
                 or (tables[0] is not None and (not torch.is_tensor(tables[0]) or tables[0].dtype != torch.long
@@ -142,21 +137,14 @@ def line_train(edges, num_nodes, dim, order, samples, negative=5, alpha=0.025, e
                                                  _lib.stream_of(edges))
         _lib.check(rc, "line_train")
     else:
-        n_rec = torch.zeros(1, dtype=torch.long)
-        if trace is not None:
-            records = torch.zeros((int(trace), 5), dtype=torch.float64)
+        records, n_rec = sgns.trace_buffer(trace, 5)
         rc = _lib.host().cogdl_host_line_train(_lib.ptr(eu), _lib.ptr(ev), _lib.ptr(ecum), m, num_nodes, _lib.ptr(ncum),
                                                _lib.ptr(table), dim, negative, order, samples, alpha, seed, workers, _lib.ptr(emb),
                                                _lib.ptr(ctx) if order == 2 else None, _lib.ptr(flags), _lib.ptr(records),
                                                0 if records is None else records.shape[0], _lib.ptr(n_rec))
         _lib.check_host(rc, "line_train")
-        if records is not None:
-            if int(n_rec) > records.shape[0]:
-                raise ValueError("line_train: trace=%d is too small for %d applied targets" % (records.shape[0], int(n_rec)))
-            records = records[:int(n_rec)]
-    bits = int(flags.item())  # the one synchronisation
-    if bits:
-        raise _lib.BackendError("line_train: %s" % "; ".join(t % num_nodes for bit, t in _FLAG_TEXT if bits & bit))
+        records = sgns.trace_records("line_train", records, n_rec)
+    sgns.raise_flags("line_train", flags, _FLAG_TEXT, num_nodes)
     out = emb if order == 1 else (emb, ctx)
     if trace is None:
         return out

@@ -19,11 +19,11 @@ the noise table and the sigmoid table are those of operators/sgns.py.
   * There is no cap on a document's length (below 2^32) and no window.  One wave per document: a batch with one very long
     document is uneven.
 """
-import numpy as np
 import torch
 
 from .. import _lib
-from .sgns import MAX_DIM, MAX_NEGATIVE, _u32, build_tables, exp_table
+from . import sgns
+from .sgns import MAX_DIM, MAX_NEGATIVE, exp_table
 from .walk import _seed
 
 # Documents per launch of the GPU's throughput mode (0 = the library's default, 8192).
@@ -61,37 +61,22 @@ def doc2vec_dbow(doc_ptr, words, num_words, dim=128, negative=5, epochs=10, alph
     alpha, min_alpha, sample, ns_exponent = float(alpha), float(min_alpha), float(sample), float(ns_exponent)
     if num_words < 1 or num_words > 2 ** 31 - 1:
         raise ValueError("doc2vec_dbow: num_words must be in [1, 2^31) (got %d)" % num_words)
-    if not 1 <= dim <= MAX_DIM:
-        raise ValueError("doc2vec_dbow: dim must be in [1, %d] (got %d)" % (MAX_DIM, dim))
-    if not 1 <= negative <= MAX_NEGATIVE:
-        raise ValueError("doc2vec_dbow: negative must be in [1, %d] (got %d)" % (MAX_NEGATIVE, negative))
-    if epochs < 1:
-        raise ValueError("doc2vec_dbow: epochs must be >= 1 (got %d)" % epochs)
-    if not (np.isfinite(alpha) and np.isfinite(min_alpha) and alpha > 0 and min_alpha >= 0):
-        raise ValueError("doc2vec_dbow: alpha must be positive and min_alpha non-negative (got %r, %r)" % (alpha, min_alpha))
-    if not (np.isfinite(sample) and sample >= 0):
-        raise ValueError("doc2vec_dbow: sample must be >= 0 (got %r)" % sample)
-    if workers < 0:
-        raise ValueError("doc2vec_dbow: workers must be >= 0 (got %d)" % workers)
+    sgns.check_range("doc2vec_dbow", "dim", dim, MAX_DIM)
+    sgns.check_range("doc2vec_dbow", "negative", negative, MAX_NEGATIVE)
+    sgns.check_schedule("doc2vec_dbow", epochs, alpha, min_alpha, sample)
+    sgns.check_workers("doc2vec_dbow", workers)
     docs_in_flight = int(DOCS_IN_FLIGHT)
     if docs_in_flight < 0:
         raise ValueError("doc2vec_dbow: DOCS_IN_FLIGHT must be >= 0 (got %d)" % docs_in_flight)
     dev = words.device
     g, t = doc_ptr.numel() - 1, words.numel()
     if init is not None:
-        for tab, rows in zip(init, (g, num_words)):
-            if (not torch.is_tensor(tab) or tab.dtype != torch.float32 or tuple(tab.shape) != (rows, dim) or tab.device != dev):
-                raise ValueError("doc2vec_dbow: init must be float32 [%d, %d] and [%d, %d] tensors on %s" % (g, dim, num_words, dim, dev))
-    if tables is not None:
-        for tab in tables:
-            if not torch.is_tensor(tab) or tab.dtype != torch.long or tuple(tab.shape) != (num_words,):
-                raise ValueError("doc2vec_dbow: tables must be two int64 [%d] tensors" % num_words)
+        sgns.check_init(init, (g, num_words), dim, dev,
+                        "doc2vec_dbow: init must be float32 [%d, %d] and [%d, %d] tensors on %s" % (g, dim, num_words, dim, dev))
+    sgns.check_tables("doc2vec_dbow", tables, num_words)
     seed = _seed(seed)
     words, doc_ptr = words.contiguous(), doc_ptr.to(dev).contiguous()
-    if tables is None:
-        valid = words[(words >= 0) & (words < num_words)]
-        tables = build_tables(torch.bincount(valid, minlength=num_words).cpu().numpy(), sample, ns_exponent)
-    keep, cum = _u32(tables[0], dev), _u32(tables[1], dev)
+    keep, cum = sgns.noise_tables(words, num_words, tables, sample, ns_exponent, dev)
     table = exp_table().to(dev)
     if init is None:
         dv, syn1 = init_tables(g, num_words, dim, seed, dev)
@@ -110,7 +95,5 @@ def doc2vec_dbow(doc_ptr, words, num_words, dim=128, negative=5, epochs=10, alph
                                                  min_alpha, _lib.ptr(keep), _lib.ptr(cum), _lib.ptr(table), seed, workers,
                                                  _lib.ptr(dv), _lib.ptr(syn1), _lib.ptr(flags))
         _lib.check_host(rc, "doc2vec_dbow")
-    bits = int(flags.item())  # the one synchronisation
-    if bits:
-        raise _lib.BackendError("doc2vec_dbow: %s" % "; ".join(t % num_words for bit, t in _FLAG_TEXT if bits & bit))
+    sgns.raise_flags("doc2vec_dbow", flags, _FLAG_TEXT, num_words)
     return dv, syn1

@@ -64,23 +64,78 @@ def _u32(t, dev):
     return torch.where(t >= 2 ** 31, t - 2 ** 32, t).to(torch.int32).to(dev).contiguous()
 
 
-def check_args(name, dim, window, negative, epochs, alpha, min_alpha, sample, workers, length):
-    if not 1 <= dim <= MAX_DIM:
-        raise ValueError("%s: dim must be in [1, %d] (got %d)" % (name, MAX_DIM, dim))
-    if not 1 <= window <= MAX_WINDOW:
-        raise ValueError("%s: window must be in [1, %d] (got %d)" % (name, MAX_WINDOW, window))
-    if not 1 <= negative <= MAX_NEGATIVE:
-        raise ValueError("%s: negative must be in [1, %d] (got %d)" % (name, MAX_NEGATIVE, negative))
+# ---- the checks and the bookkeeping the three trainers share (skipgram here, operators/pvdbow.py, operators/line.py)
+
+def check_range(name, what, value, hi):
+    if not 1 <= value <= hi:
+        raise ValueError("%s: %s must be in [1, %d] (got %d)" % (name, what, hi, value))
+
+
+def check_schedule(name, epochs, alpha, min_alpha, sample):
     if epochs < 1:
         raise ValueError("%s: epochs must be >= 1 (got %d)" % (name, epochs))
     if not (np.isfinite(alpha) and np.isfinite(min_alpha) and alpha > 0 and min_alpha >= 0):
         raise ValueError("%s: alpha must be positive and min_alpha non-negative (got %r, %r)" % (name, alpha, min_alpha))
     if not (np.isfinite(sample) and sample >= 0):
         raise ValueError("%s: sample must be >= 0 (got %r)" % (name, sample))
+
+
+def check_workers(name, workers):
     if workers < 0:
         raise ValueError("%s: workers must be >= 0 (got %d)" % (name, workers))
+
+
+def check_args(name, dim, window, negative, epochs, alpha, min_alpha, sample, workers, length):
+    check_range(name, "dim", dim, MAX_DIM)
+    check_range(name, "window", window, MAX_WINDOW)
+    check_range(name, "negative", negative, MAX_NEGATIVE)
+    check_schedule(name, epochs, alpha, min_alpha, sample)
+    check_workers(name, workers)
     if length > MAX_LENGTH:
         raise ValueError("%s: rows of more than %d tokens are not supported (got %d)" % (name, MAX_LENGTH, length))
+
+
+def check_init(init, rows, dim, dev, message):
+    """Every table of `init` is a float32 [rows[i], dim] tensor on `dev`, or ValueError(message)."""
+    for t, n in zip(init, rows):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (n, dim) or t.device != dev:
+            raise ValueError(message)
+
+
+def noise_tables(ids, num_ids, tables, sample, ns_exponent, dev):
+    """(keep, cum) on `dev` in the kernels' uint32 format: the caller's `tables` (checked), or built from the counts of the
+    valid `ids`."""
+    if tables is None:
+        valid = ids[(ids >= 0) & (ids < num_ids)]
+        tables = build_tables(torch.bincount(valid, minlength=num_ids).cpu().numpy(), sample, ns_exponent)
+    return _u32(tables[0], dev), _u32(tables[1], dev)
+
+
+def check_tables(name, tables, num_ids):
+    for t in tables or ():
+        if not torch.is_tensor(t) or t.dtype != torch.long or tuple(t.shape) != (num_ids,):
+            raise ValueError("%s: tables must be two int64 [%d] tensors" % (name, num_ids))
+
+
+def trace_buffer(trace, width):
+    """(records or None, the host twin's counter of applied targets) for `trace=n` records of `width` fields."""
+    return (None if trace is None else torch.zeros((int(trace), width), dtype=torch.float64)), torch.zeros(1, dtype=torch.long)
+
+
+def trace_records(name, records, n_rec):
+    if records is None:
+        return None
+    if int(n_rec) > records.shape[0]:
+        raise ValueError("%s: trace=%d is too small for %d applied targets" % (name, records.shape[0], int(n_rec)))
+    return records[:int(n_rec)]
+
+
+def raise_flags(name, flags, flag_text, num_ids):
+    """The error word of a training call -> BackendError naming every raised flag.  Reading it is the call's one
+    synchronisation."""
+    bits = int(flags.item())
+    if bits:
+        raise _lib.BackendError("%s: %s" % (name, "; ".join(t % num_ids for bit, t in flag_text if bits & bit)))
 
 
 def init_tables(num_nodes, dim, seed, device):
@@ -121,19 +176,11 @@ def skipgram(walks, num_nodes, dim=128, window=5, negative=5, epochs=5, alpha=0.
     if trace is not None and (dev.type != "cpu" or workers != 1):
         raise ValueError("skipgram: trace needs CPU walks and workers=1")
     if init is not None:
-        for t in init:
-            if (not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (num_nodes, dim) or t.device != dev):
-                raise ValueError("skipgram: init must be two float32 [%d, %d] tensors on %s" % (num_nodes, dim, dev))
-    if tables is not None:
-        for t in tables:
-            if not torch.is_tensor(t) or t.dtype != torch.long or tuple(t.shape) != (num_nodes,):
-                raise ValueError("skipgram: tables must be two int64 [%d] tensors" % num_nodes)
+        check_init(init, (num_nodes, num_nodes), dim, dev, "skipgram: init must be two float32 [%d, %d] tensors on %s" % (num_nodes, dim, dev))
+    check_tables("skipgram", tables, num_nodes)
     seed = _seed(seed)
     walks = walks.contiguous()
-    if tables is None:
-        valid = walks[(walks >= 0) & (walks < num_nodes)]
-        tables = build_tables(torch.bincount(valid, minlength=num_nodes).cpu().numpy(), sample, ns_exponent)
-    keep, cum = _u32(tables[0], dev), _u32(tables[1], dev)
+    keep, cum = noise_tables(walks, num_nodes, tables, sample, ns_exponent, dev)
     table = exp_table().to(dev)
     if init is None:
         syn0, syn1 = init_tables(num_nodes, dim, seed, dev)
@@ -149,19 +196,12 @@ def skipgram(walks, num_nodes, dim=128, window=5, negative=5, epochs=5, alpha=0.
                                                  _lib.stream_of(walks))
         _lib.check(rc, "skipgram")
     else:
-        n_rec = torch.zeros(1, dtype=torch.long)
-        if trace is not None:
-            records = torch.zeros((int(trace), 6), dtype=torch.float64)
+        records, n_rec = trace_buffer(trace, 6)
         rc = _lib.host().cogdl_host_sgns_train(_lib.ptr(walks), w, length, num_nodes, dim, window, negative, epochs, alpha,
                                                min_alpha, _lib.ptr(keep), _lib.ptr(cum), _lib.ptr(table), seed, workers,
                                                _lib.ptr(syn0), _lib.ptr(syn1), _lib.ptr(flags), _lib.ptr(records),
                                                0 if records is None else records.shape[0], _lib.ptr(n_rec))
         _lib.check_host(rc, "skipgram")
-        if records is not None:
-            if int(n_rec) > records.shape[0]:
-                raise ValueError("skipgram: trace=%d is too small for %d applied targets" % (records.shape[0], int(n_rec)))
-            records = records[:int(n_rec)]
-    bits = int(flags.item())  # the one synchronisation
-    if bits:
-        raise _lib.BackendError("skipgram: %s" % "; ".join(t % num_nodes for bit, t in _FLAG_TEXT if bits & bit))
+        records = trace_records("skipgram", records, n_rec)
+    raise_flags("skipgram", flags, _FLAG_TEXT, num_nodes)
     return (syn0, syn1) if trace is None else (syn0, syn1, records)

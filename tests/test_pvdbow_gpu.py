@@ -27,6 +27,20 @@ def test_serial_mode_equals_the_host_twin_bit_for_bit(case):
     assert torch.equal(host[1], gpu[1].cpu()), "syn1: max difference %g" % float((host[1] - gpu[1].cpu()).abs().max())
 
 
+def test_serial_mode_with_the_store_row_update_equals_the_host_twin_bit_for_bit():
+    """Tuning key 17 = 1: syn1 rows are updated by write-through stores of (loaded + delta), which in serial order is the
+    law's sum."""
+    doc_ptr, words = corpus()
+    host = doc2vec_dbow(doc_ptr, words, VOCAB, dim=65, negative=5, sample=0.0, **KW)
+    _lib.hip().cogdl_hip_set_tuning(17, 1)
+    try:
+        gpu = doc2vec_dbow(doc_ptr.to(DEV), words.to(DEV), VOCAB, dim=65, negative=5, sample=0.0, **KW)
+    finally:
+        _lib.hip().cogdl_hip_set_tuning(17, 0)
+    assert torch.equal(host[0], gpu[0].cpu()), "dv: max difference %g" % float((host[0] - gpu[0].cpu()).abs().max())
+    assert torch.equal(host[1], gpu[1].cpu()), "syn1: max difference %g" % float((host[1] - gpu[1].cpu()).abs().max())
+
+
 def test_serial_mode_continues_from_the_callers_tables_and_runs_twice_alike():
     doc_ptr, words = corpus()
     kw = dict(dim=65, negative=5, epochs=1, seed=3, workers=1)

@@ -31,6 +31,21 @@ def test_serial_mode_equals_the_host_twin_bit_for_bit(case):
     assert torch.equal(host[1], gpu[1].cpu()), "syn1: max difference %g" % float((host[1] - gpu[1].cpu()).abs().max())
 
 
+def test_serial_mode_with_the_store_row_update_equals_the_host_twin_bit_for_bit():
+    """Tuning key 17 = 1: rows are updated by write-through stores of (loaded + delta), which in serial order is the law's sum.
+    V = 3 against 4 negatives: most pairs repeat a target, which is re-read after the wave's own store."""
+    walks = corpus(7, 5, 3)
+    kw = dict(dim=65, window=3, negative=4, epochs=2, alpha=0.05, sample=0.0, seed=11, workers=1)
+    host = skipgram(walks, 3, **kw)
+    _lib.hip().cogdl_hip_set_tuning(17, 1)
+    try:
+        gpu = skipgram(walks.to(DEV), 3, **kw)
+    finally:
+        _lib.hip().cogdl_hip_set_tuning(17, 0)
+    assert torch.equal(host[0], gpu[0].cpu()), "syn0: max difference %g" % float((host[0] - gpu[0].cpu()).abs().max())
+    assert torch.equal(host[1], gpu[1].cpu()), "syn1: max difference %g" % float((host[1] - gpu[1].cpu()).abs().max())
+
+
 def test_serial_mode_continues_from_the_callers_tables_and_runs_twice_alike():
     walks = corpus(64, 40, 500)
     kw = dict(dim=65, window=5, negative=5, epochs=1, seed=3, workers=1)
