@@ -198,6 +198,12 @@ HIP_SIGNATURES = {
     # edge-sampled skip-gram training, LINE orders 1 and 2 (csrc/line.hip)
     "cogdl_hip_line_train": ([_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _i64, _f64, _u64, _i32, _i64, _vp, _vp, _vp,
                               _vp], _i32),
+    # multiplex attention embedding, GATNE's model step (csrc/multiplex.hip)
+    "cogdl_hip_multiplex_fwd": ([_vp] * 8 + [_i64] * 7 + [_vp] * 6 + [_vp], _i32),
+    "cogdl_hip_multiplex_bwd_sample": ([_vp] * 10 + [_i64] * 5 + [_vp] * 4 + [_vp], _i32),
+    "cogdl_hip_multiplex_bwd_weights": ([_vp] * 8 + [_i64] * 7 + [_vp] * 3 + [_vp], _i32),
+    "cogdl_hip_multiplex_bwd_node": ([_vp] * 3 + [_i64] * 5 + [_vp, _vp], _i32),
+    "cogdl_hip_multiplex_bwd_type": ([_vp] * 3 + [_i64] * 7 + [_vp, _vp], _i32),
 }
 
 MAX_SEGMENTS = 64  # COGDL_HIP_MAX_SEGMENTS

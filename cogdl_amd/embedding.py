@@ -9,6 +9,7 @@ library's skip-gram operator -- what the reference's DeepWalk / Node2vec do thro
     prone(graph_or_csr, dim, step, mu, theta)                               -> float32 [N, dim]
     graph2vec(graphs, dim, rounds, min_count, epochs)                       -> float32 [G, dim]  (one row per graph)
     line(graph_or_csr, dim, walk_length, walk_num, negative, alpha, order)  -> float32 [N, dim]
+    gatne(layers, dim, walk_length, walk_num, window, epochs, batch_size, ...) -> (float32 [T, N, dim], nodes int64 [N])
 
 `graph_or_csr` is a cogdl Graph (its row_indptr / col_indices are used on the device they live on) or an
 (indptr, indices) pair of int64 tensors.  Each of the walk_num passes starts one walk at every node, in an order shuffled
@@ -328,6 +329,163 @@ def prone(graph_or_csr, dim=128, step=5, mu=0.2, theta=0.5, seed=None):
     if step == 1:
         return feat
     return dense_embedding(spectral_filter("prone", rowptr, col, feat, order=step, mu=mu, s=theta))
+
+
+def gatne_layer_csr(edges, num_ids):
+    """The undirected simple graph of one layer's raw edge list (int64 [E, 2]) over the ids [0, num_ids), as nx.Graph builds it:
+    both directions, parallel edges collapsed, a self-loop kept once -> (indptr int64 [num_ids + 1], indices int64, ascending per
+    row)."""
+    a, b = edges[:, 0], edges[:, 1]
+    keys = torch.unique(torch.cat([a * num_ids + b, b * num_ids + a]))
+    src, dst = keys // num_ids, keys % num_ids
+    indptr = torch.zeros(num_ids + 1, dtype=torch.long, device=edges.device)
+    torch.cumsum(torch.bincount(src, minlength=num_ids), 0, out=indptr[1:])
+    return indptr, dst.contiguous()
+
+
+def gatne_vocabulary(walks, num_ids):
+    """The nodes that occur in a walk, by descending count, ties in ascending id -> (nodes int64 [N], index_of int64 [num_ids]
+    with -1 for an id that is in no walk)."""
+    count = torch.zeros(num_ids, dtype=torch.long, device=walks[0].device)
+    for w in walks:
+        count += torch.bincount(w[w >= 0].reshape(-1), minlength=num_ids)
+    present = torch.nonzero(count > 0).flatten()  # ascending ids
+    order = torch.sort(count[present], descending=True, stable=True)[1]
+    nodes = present[order].contiguous()
+    index_of = torch.full((num_ids,), -1, dtype=torch.long, device=nodes.device)
+    index_of[nodes] = torch.arange(nodes.numel(), device=nodes.device)
+    return nodes, index_of
+
+
+def gatne_pairs(walks, window=5):
+    """The training pairs of a list of index walks (one int64 [W_t, L] tensor per layer, -1 = past the walk's end), by slicing:
+    every position with its window // 2 predecessors and successors (generate_pairs, gatne.py:338-349)
+    -> (center, context, layer), int64 [P] each, in no particular order."""
+    skip = int(window) // 2
+    center, context, layer = [], [], []
+    for t, w in enumerate(walks):
+        for j in range(1, min(skip, w.shape[1] - 1) + 1):
+            for c, x in ((w[:, j:], w[:, :-j]), (w[:, :-j], w[:, j:])):
+                ok = (c >= 0) & (x >= 0)
+                center.append(c[ok])
+                context.append(x[ok])
+                layer.append(torch.full((center[-1].numel(),), t, dtype=torch.long, device=w.device))
+    if not center:
+        empty = torch.zeros(0, dtype=torch.long, device=walks[0].device if walks else None)
+        return empty, empty.clone(), empty.clone()
+    return torch.cat(center), torch.cat(context), torch.cat(layer)
+
+
+def gatne_neighbors(layers, num_nodes, samples, generator=None):
+    """The [N, T, S] neighbour table of GATNE (gatne.py:130-146) from the layers' raw edge lists in index space (int64 [E_t, 2]):
+    both directions, with multiplicity, in edge order (forward entries before backward ones).  A node without a neighbour of a
+    type gets itself S times; one with fewer than S gets all of them, then uniform draws with replacement from them; one with
+    more gets S uniform draws with replacement; one with exactly S gets them as they are.  -> int64 [N, T, S]."""
+    n, s = int(num_nodes), int(samples)
+    dev = layers[0].device
+    slot = torch.arange(s, device=dev).view(1, s)
+    me = torch.arange(n, device=dev).view(n, 1).expand(n, s)
+    out = []
+    for e in layers:
+        src, dst = torch.cat([e[:, 0], e[:, 1]]), torch.cat([e[:, 1], e[:, 0]])
+        order = torch.sort(src, stable=True)[1]
+        dst = dst[order]
+        deg = torch.bincount(src, minlength=n)
+        ptr = torch.cumsum(deg, 0) - deg
+        deg = deg.view(n, 1)
+        r = torch.rand((n, s), generator=generator, device=dev, dtype=torch.float64)
+        drawn = torch.minimum((r * deg).long(), (deg - 1).clamp_min(0))
+        pick = torch.where((deg > s) | (slot >= deg), drawn, slot.expand(n, s))
+        if dst.numel():
+            got = dst[(ptr.view(n, 1) + pick).clamp(0, dst.numel() - 1)]
+        else:
+            got = me
+        out.append(torch.where(deg > 0, got, me))
+    return torch.stack(out, dim=1).contiguous()
+
+
+def gatne(layers, dim=200, walk_length=10, walk_num=10, window=5, epochs=20, batch_size=256, edge_dim=10, att_dim=20, negative=5,
+          neighbor_samples=10, lr=1e-4, seed=None, device=None, return_loss=False):
+    """GATNE-T (cogdl/models/emb/gatne.py:111-194) on a multiplex network: `layers` is a list of int64 [E_t, 2] edge lists, one
+    per edge type, over non-negative node ids -> (emb float32 [T, N, dim], nodes int64 [N]); emb[t, k] is the embedding of node
+    nodes[k] under edge type t, rows of unit norm.  With return_loss=True also the list of the mean loss of each epoch.
+
+    Per layer the undirected simple graph (gatne_layer_csr) is walked walk_num times from every node in shuffled order
+    (random_walk); the vocabulary is the nodes that occur in a walk, by descending count (ties: ascending id, where the reference
+    keeps first appearance); the pairs come from gatne_pairs with the given window (the reference's forward always uses 5), the
+    [N, T, S] neighbour table from gatne_neighbors.  A step takes a shuffled slice of the pairs, embeds the centres with
+    operators.multiplex.multiplex_embed, scores them against the context table with operators.kgscore.sampled_scores on
+    [context | negatives] (negatives from torch.multinomial over the rank weights log(k + 2) - log(k + 1)), takes
+    -mean(logsigmoid(pos) + SUM logsigmoid(-neg)) and applies torch.optim.Adam(lr).  Initial values follow the reference:
+    uniform(-1, 1) for the two tables, normal with std 1 / sqrt(dim) for the rest.  The final embeddings are one batched call of
+    N T samples.  Everything after the edge lists stays on `device` (default: the GPU where there is one).  lr defaults to the
+    reference's 1e-4, with which a small network barely moves in a few epochs.  `seed` makes a run reproducible on one device."""
+    from .operators.kgscore import sampled_scores
+    from .operators.multiplex import multiplex_embed
+
+    dev = torch.device(device) if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    layers = [torch.as_tensor(e).long().reshape(-1, 2).to(dev) for e in layers]
+    if not layers or any(e.numel() == 0 for e in layers):
+        raise ValueError("gatne: needs at least one layer, and every layer at least one edge")
+    walk_num, walk_length, epochs, batch_size = int(walk_num), int(walk_length), int(epochs), int(batch_size)
+    dim, edge_dim, att_dim, negative, samples = int(dim), int(edge_dim), int(att_dim), int(negative), int(neighbor_samples)
+    if min(walk_num, walk_length, batch_size, dim, edge_dim, att_dim, negative, samples) < 1 or epochs < 0:
+        raise ValueError("gatne: walk_num, walk_length, batch_size, dim, edge_dim, att_dim, negative and neighbor_samples must be "
+                         "at least 1, epochs at least 0")
+    if int(min(int(e.min()) for e in layers)) < 0:
+        raise ValueError("gatne: a negative node id")
+    num_ids = max(int(e.max()) for e in layers) + 1
+    seed = _seed(seed)
+    t_count = len(layers)
+    cpu_gen = torch.Generator().manual_seed(seed % (2 ** 63))
+    walks = []
+    for t, e in enumerate(layers):
+        indptr, indices = gatne_layer_csr(e, num_ids)
+        members = torch.nonzero(indptr[1:] > indptr[:-1]).flatten().cpu()
+        start = torch.cat([members[torch.randperm(members.numel(), generator=cpu_gen)] for _ in range(walk_num)]).to(dev)
+        walks.append(random_walk(indptr, indices, start, walk_length, seed=(seed + 1 + t) & (2 ** 64 - 1)))
+    nodes, index_of = gatne_vocabulary(walks, num_ids)
+    n = nodes.numel()
+    center, context, layer = gatne_pairs([index_of[w] for w in walks], window)
+    gen = torch.Generator(device=dev).manual_seed((seed + 1 + t_count) % (2 ** 63))
+    neigh = gatne_neighbors([index_of[e] for e in layers], n, samples, gen)
+    neigh32 = neigh.to(torch.int32)
+
+    std = 1.0 / math.sqrt(dim)
+    f32 = dict(dtype=torch.float32, device=dev)
+    node_emb = (torch.rand((n, dim), generator=gen, **f32) * 2 - 1).requires_grad_()
+    type_emb = (torch.rand((n, t_count, edge_dim), generator=gen, **f32) * 2 - 1).requires_grad_()
+    trans_w = (torch.randn((t_count, edge_dim, dim), generator=gen, **f32) * std).requires_grad_()
+    att_w1 = (torch.randn((t_count, edge_dim, att_dim), generator=gen, **f32) * std).requires_grad_()
+    att_w2 = (torch.randn((t_count, att_dim), generator=gen, **f32) * std).requires_grad_()
+    ctx_w = (torch.randn((n, dim), generator=gen, **f32) * std).requires_grad_()
+    params = [node_emb, type_emb, trans_w, att_w1, att_w2]
+    rank = torch.arange(n, dtype=torch.float64, device=dev)
+    noise = (torch.log(rank + 2) - torch.log(rank + 1)).float()
+    opt = torch.optim.Adam(params + [ctx_w], lr=lr)
+    n_pairs = center.numel()
+    losses = []
+    for _ in range(epochs):
+        perm = torch.randperm(n_pairs, generator=gen, device=dev)
+        total = torch.zeros((), dtype=torch.float64, device=dev)
+        for lo in range(0, n_pairs, batch_size):
+            pick = perm[lo:lo + batch_size]
+            x, y, t = center[pick], context[pick], layer[pick]
+            negs = torch.multinomial(noise, negative * x.numel(), replacement=True, generator=gen).view(-1, negative)
+            opt.zero_grad(set_to_none=True)
+            embs = multiplex_embed(*params, neigh32, x, t, check=False)  # (every id comes from this function's own tables)
+            scores = sampled_scores(embs, ctx_w, torch.cat([y.unsqueeze(1), negs], dim=1), "dot", check=False)
+            logsig = torch.nn.functional.logsigmoid
+            loss = -(logsig(scores[:, 0]) + logsig(-scores[:, 1:]).sum(1)).mean()
+            loss.backward()
+            opt.step()
+            total += loss.detach().double() * x.numel()
+        losses.append(float(total / max(n_pairs, 1)))
+    with torch.no_grad():
+        every = torch.arange(n, device=dev).repeat(t_count)
+        kinds = torch.repeat_interleave(torch.arange(t_count, device=dev), n)
+        emb = multiplex_embed(*params, neigh32, every, kinds, check=False).view(t_count, n, dim)
+    return (emb, nodes, losses) if return_loss else (emb, nodes)
 
 
 def undirected_edges(row, col, num_nodes, weight=None):

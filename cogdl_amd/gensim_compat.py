@@ -50,6 +50,21 @@ class KeyedVectors(object):
         return len(self.index_to_key)
 
 
+class Vocab(object):
+    """gensim 3's per-word record, which cogdl/models/emb/gatne.py:4,363 still builds: attributes from keywords (`count`,
+    `index`), ordered by count."""
+
+    def __init__(self, **kwargs):
+        self.count = 0
+        self.__dict__.update(kwargs)
+
+    def __lt__(self, other):
+        return self.count < other.count
+
+    def __str__(self):
+        return "%s<%s>" % (self.__class__.__name__, ", ".join("%s:%r" % kv for kv in sorted(self.__dict__.items())))
+
+
 class Word2Vec(object):
     def __init__(self, sentences=None, vector_size=100, alpha=0.025, window=5, min_count=5, sample=1e-3, seed=None, workers=3,
                  min_alpha=1e-4, sg=0, hs=0, negative=5, ns_exponent=0.75, epochs=5, device=None):
@@ -169,7 +184,7 @@ def _submodule(name, **names):
 # the module layout of gensim that the reference imports from
 models = _submodule("models", Word2Vec=Word2Vec, KeyedVectors=KeyedVectors, Doc2Vec=Doc2Vec)
 models.word2vec = _submodule("models.word2vec", Word2Vec=Word2Vec)
-models.keyedvectors = _submodule("models.keyedvectors", KeyedVectors=KeyedVectors)
+models.keyedvectors = _submodule("models.keyedvectors", KeyedVectors=KeyedVectors, Vocab=Vocab)
 models.doc2vec = _submodule("models.doc2vec", Doc2Vec=Doc2Vec, TaggedDocument=TaggedDocument)
 __path__ = []  # (a package as far as `import gensim.models` is concerned; the submodules are registered by install())
 

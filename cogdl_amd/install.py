@@ -41,7 +41,7 @@ _finder = None
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
             metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False, readout=False,
             relational=False, genconv=False, disengcn=False, contrast=False, netsmf=False, metapath=False, prone=False,
-            kg_eval=False, kg_train=False, graph2vec=False, kg_sample=False, line=False):
+            kg_eval=False, kg_train=False, graph2vec=False, kg_sample=False, gatne=False, line=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -196,6 +196,17 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     alias_draw per edge and per negative; the return value is the reference's (float64 numpy [N, width] with L2-normalised
     rows, or the dict with return_dict=True).  Edge weights that are not all finite and positive, a graph without edges, an
     order outside {1, 2, 3} and dimension < 2 with order 3 reach the reference's forward.
+    gatne=True rebinds GATNE.forward in cogdl.models.emb.gatne (opt-in: the draws are Philox's and torch's, not `random`'s and
+    numpy's; ties in the vocabulary order go in ascending node id where the reference keeps first appearance; a trailing batch
+    of one pair and a network of one edge type train here, where the reference's module raises; `worker` is ignored) to
+    cogdl_amd.gatne_compat: cogdl_amd.embedding.gatne builds the layers' graphs, walks them with the library's random_walk,
+    slices the pairs, draws the [N, T, S] neighbour table once and trains with one multiplex_embed and one sampled_scores call
+    per step (HIP kernels for CUDA tensors: the model step is one forward launch without the reference's [B, T, S, T, U] gather,
+    and no gradient uses a float atomic; the torch composition and the host twins on the CPU) under torch.optim.Adam(lr=1e-4);
+    the final embeddings are one batched call.  The return value is the reference's ({edge type: {node id: float32 numpy
+    [dimension]}}).  The reference module imports gensim.models.keyedvectors.Vocab, so where gensim is absent
+    cogdl_amd.gensim_compat is registered first, as metapath=True does.  A schema other than None, an empty network_data, a
+    layer without edges and node ids that are not non-negative integers reach the reference's forward.
     linear=True additionally routes torch.nn.functional.linear -- i.e. the unchanged nn.Linear inside every CogDL
     layer -- through cogdl_amd.linear (hand-written MFMA weight gradient for full-graph shapes)."""
     global _finder
@@ -338,6 +349,13 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
         _import_target(line_compat._MODULE, "line")
         if not line_compat.install():
             raise _lib_error("install(line=True): LINE.forward could not be rebound")
+    if gatne:
+        from . import gatne_compat
+
+        _serve_gensim_where_absent()  # (cogdl.models.emb.gatne imports gensim.models.keyedvectors.Vocab)
+        _import_target(gatne_compat._MODULE, "gatne")
+        if not gatne_compat.install():
+            raise _lib_error("install(gatne=True): GATNE.forward could not be rebound")
     su =sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):

@@ -41,6 +41,8 @@
     pvdbow.py        doc2vec_dbow (also exported here)                 (gensim's Doc2Vec(dm=0) in models/emb/graph2vec.py:99-109)
     line.py          line_train (also exported here)                   (LINE._train_line, models/emb/line.py:127-158)
 
+    multiplex.py     multiplex_embed (also exported here)              (GATNEModel.forward, models/emb/gatne.py:221-241)
+
     ops.py           scatter_add, op_aggr, s_*_e_sum / s_*_e_mean (fused HIP), s_*_e, s_*_t   (cogdl/operators/ops.py)
 
 Submodules are imported lazily: GPU modules load libcogdl_hip.so at import and raise if it
@@ -113,4 +115,8 @@ def __getattr__(name):
         from . import line
 
         return line.line_train
+    if name == "multiplex_embed":
+        from . import multiplex
+
+        return multiplex.multiplex_embed
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

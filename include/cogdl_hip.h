@@ -1328,6 +1328,49 @@ COGDL_API int cogdl_hip_line_train(const int64_t *eu, const int64_t *ev, const i
                        uint64_t seed, int workers, int64_t samples_in_flight, float *emb, float *ctx, int *flags,
                        void *stream);
 
+/* -------------------------------------------------------------------------------------------------------------------
+ * Fused multiplex (typed-edge) attention embedding: GATNE's model step (csrc/multiplex.hip).  For sample b with
+ * x = inputs[b], t = types[b]:
+ *     c[i, :] = SUM_s type_emb[neigh[x, i, s], i, :]        h = tanh(c att_w1[t])        e = h att_w2[t]
+ *     att = softmax_i(e)        m = att c        y = node_emb[x] + m trans_w[t]        out[b] = y / max(||y||, 1e-12)
+ * node_emb fp32 [N, D], type_emb fp32 [N, T, U], trans_w fp32 [T, U, D], att_w1 fp32 [T, U, A], att_w2 fp32 [T, A],
+ * neigh int32 [N, T, S], inputs / types int32 [B].  Nothing of size [B, T, S, U] is written.  The order of every float32
+ * operation is csrc/multiplex_law.h's; there are no float atomics: results are equal from run to run and do not depend on the
+ * launch geometry.  tanh and exp are the device library's (no host twin).
+ *   cogdl_hip_multiplex_fwd         one launch, one wave per sample.  Writes out [B, D] and what the backward reads: c [B, T, U],
+ *                                   h [B, T, A], att [B, T], m [B, U], nrm [B].  A sample whose input, type or any of its T S
+ *                                   neighbour ids is out of range gets out = NaN and nrm = -1; no id is followed unchecked.
+ *   cogdl_hip_multiplex_bwd_sample  g fp32 [B, D] -> g_y [B, D], g_c [B, T, U], g_pre [B, T, A], g_e [B, T]; zeros for a sample
+ *                                   with nrm < 0.
+ *   cogdl_hip_multiplex_bwd_weights grad trans_w, grad att_w1, grad att_w2 (each may be NULL: not computed) from the lists of
+ *                                   the samples of each type.
+ *   cogdl_hip_multiplex_bwd_node    grad node_emb [N, D] from the lists of the samples of each input node.
+ *   cogdl_hip_multiplex_bwd_type    grad type_emb [N, T, U] from the lists of the neighbour slots of each key n T + i.
+ * Lists: occ_ptr int32 points at the first bound of the family (T + 1, N + 1, N T + 1 bounds are read), occ_pos int32 [P] is
+ * the whole position array of the inverted index; a list entry is pos_base + b (weights, node) or pos_base + (b T + i) S + s
+ * (type), ascending.  Entries outside their range are passed over, bounds are clamped to [0, P]; every element of every
+ * gradient is written, +0 for an empty list: no memset precedes the launches.
+ * Limits: 1 <= T <= 16, 1 <= S, U, A <= 64, 1 <= D <= 1024, B T S + 2 B and N T + N + T below 2^31 - 1 (COGDL_HIP_ERANGE
+ * beyond); a negative or zero T, S, U, A, D: COGDL_HIP_EINVAL; B == 0 (N == 0 for the two table gradients): success, nothing
+ * launched; a NULL pointer to a non-empty operand: COGDL_HIP_EINVAL; pointers aligned to 4 bytes (COGDL_HIP_EALIGN otherwise).
+ * ------------------------------------------------------------------------------------------------------------------- */
+COGDL_API int cogdl_hip_multiplex_fwd(const float *node_emb, const float *type_emb, const float *trans_w, const float *att_w1,
+                       const float *att_w2, const int32_t *neigh, const int32_t *inputs, const int32_t *types, int64_t B,
+                       int64_t N, int64_t T, int64_t S, int64_t U, int64_t A, int64_t D, float *c, float *h, float *att, float *m,
+                       float *nrm, float *out, void *stream);
+COGDL_API int cogdl_hip_multiplex_bwd_sample(const float *trans_w, const float *att_w1, const float *att_w2, const int32_t *types,
+                       const float *g, const float *out, const float *nrm, const float *c, const float *h, const float *att,
+                       int64_t B, int64_t T, int64_t U, int64_t A, int64_t D, float *g_y, float *g_c, float *g_pre, float *g_e,
+                       void *stream);
+COGDL_API int cogdl_hip_multiplex_bwd_weights(const float *m, const float *g_y, const float *c, const float *g_pre,
+                       const float *g_e, const float *h, const int32_t *occ_ptr, const int32_t *occ_pos, int64_t pos_base,
+                       int64_t P, int64_t B, int64_t T, int64_t U, int64_t A, int64_t D, float *g_trans, float *g_w1, float *g_w2,
+                       void *stream);
+COGDL_API int cogdl_hip_multiplex_bwd_node(const float *g_y, const int32_t *occ_ptr, const int32_t *occ_pos, int64_t pos_base,
+                       int64_t P, int64_t B, int64_t N, int64_t D, float *g_node, void *stream);
+COGDL_API int cogdl_hip_multiplex_bwd_type(const float *g_c, const int32_t *occ_ptr, const int32_t *occ_pos, int64_t pos_base,
+                       int64_t P, int64_t B, int64_t N, int64_t T, int64_t S, int64_t U, float *g_type, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
