@@ -204,6 +204,12 @@ HIP_SIGNATURES = {
     "cogdl_hip_multiplex_bwd_weights": ([_vp] * 8 + [_i64] * 7 + [_vp] * 3 + [_vp], _i32),
     "cogdl_hip_multiplex_bwd_node": ([_vp] * 3 + [_i64] * 5 + [_vp, _vp], _i32),
     "cogdl_hip_multiplex_bwd_type": ([_vp] * 3 + [_i64] * 7 + [_vp, _vp], _i32),
+    # activation compression (csrc/actq.hip)
+    "cogdl_hip_actq_quantize": ([_vp, _i64, _i32, _i32, _u64, _u64, _vp, _vp, _vp], _i32),
+    "cogdl_hip_actq_dequantize": ([_vp, _vp, _i64, _i32, _i32, _vp, _vp], _i32),
+    "cogdl_hip_relu_mask": ([_vp, _i64, _vp, _vp, _vp], _i32),
+    "cogdl_hip_mask_apply": ([_vp, _vp, _i64, _vp, _vp], _i32),
+    "cogdl_hip_drop_apply": ([_vp, _i64, _u64, _u64, _u32, _f32, _vp, _vp], _i32),
 }
 
 MAX_SEGMENTS = 64  # COGDL_HIP_MAX_SEGMENTS
@@ -252,6 +258,11 @@ HOST_SIGNATURES = {
                                   _i32),
     "cogdl_host_line_train": ([_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _i64, _f64, _u64, _i32, _vp, _vp, _vp, _vp,
                                _i64, _vp], _i32),
+    "cogdl_host_actq_quantize": ([_vp, _i64, _i32, _i32, _u64, _u64, _vp, _vp], _i32),
+    "cogdl_host_actq_dequantize": ([_vp, _vp, _i64, _i32, _i32, _vp], _i32),
+    "cogdl_host_relu_mask": ([_vp, _i64, _vp, _vp], _i32),
+    "cogdl_host_mask_apply": ([_vp, _vp, _i64, _vp], _i32),
+    "cogdl_host_drop_apply": ([_vp, _i64, _u64, _u64, _u32, _f32, _vp], _i32),
 }
 
 EUNSUPPORTED = 7  # COGDL_HIP_EUNSUPPORTED

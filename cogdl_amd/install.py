@@ -41,7 +41,7 @@ _finder = None
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
             metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False, readout=False,
             relational=False, genconv=False, disengcn=False, contrast=False, netsmf=False, metapath=False, prone=False,
-            kg_eval=False, kg_train=False, graph2vec=False, kg_sample=False, gatne=False, line=False):
+            kg_eval=False, kg_train=False, graph2vec=False, kg_sample=False, gatne=False, actnn=False, line=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -207,6 +207,17 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     [dimension]}}).  The reference module imports gensim.models.keyedvectors.Vocab, so where gensim is absent
     cogdl_amd.gensim_compat is registered first, as metapath=True does.  A schema other than None, an empty network_data, a
     layer without edges and node ids that are not non-negative integers reach the reference's forward.
+    actnn=True registers cogdl_amd.actnn_compat as `actnn` (with actnn.ops, actnn.conf, actnn.qscheme, actnn.layers and
+    actnn.utils) where the real package cannot be imported, as metis=True does for metis: the reference's `--actnn` family --
+    the actgcn model, graphsage / gcnii with actnn=True, cogdl/operators/linear.py with its random projection,
+    cogdl/layers/act*_layer.py and Trainer(actnn=True) -- imports and trains.  What a layer saves for its backward pass is
+    held by the library's activation-compression operators (cogdl_amd/operators/actq.py; HIP kernels for CUDA tensors, the
+    OpenMP host twin otherwise): the input of a QLinear, of a QBatchNorm1d and of csrspmm(actnn=True) in 2 bits per element
+    (config.activation_compression_bits), the state of a QReLU in one bit per element, and a QDropout saves nothing -- its
+    mask is regenerated from a counter.  This is not ActNN's arithmetic (INTEGRATION.md lists every deviation): groups of
+    the flattened tensor, float32 (min, step) pairs, Philox draws keyed by torch.initial_seed(), float32 compute only, and
+    the optimisation levels L3 and above are served as L2 with one warning.  A training step that uses it must not be
+    captured in a graph (a replay would repeat one noise draw).
     linear=True additionally routes torch.nn.functional.linear -- i.e. the unchanged nn.Linear inside every CogDL
     layer -- through cogdl_amd.linear (hand-written MFMA weight gradient for full-graph shapes)."""
     global _finder
@@ -260,6 +271,11 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
         _serve_where_absent("metis")
     if torch_sparse:
         _serve_where_absent("torch_sparse")
+    if actnn:
+        from . import actnn_compat
+
+        _serve_where_absent("actnn")
+        actnn_compat.register(_rebind)
     if random_walk:
         _rebind_random_walker()
     if ppr:

@@ -43,6 +43,11 @@
 
     multiplex.py     multiplex_embed (also exported here)              (GATNEModel.forward, models/emb/gatne.py:221-241)
 
+    actq.py          quantize, dequantize, relu_packed, dropout_regen, linear_q (also exported here)
+                                                                       (actnn.ops / actnn.layers as the reference uses them:
+                                                                        operators/linear.py, operators/spmm.py:89-133,
+                                                                        layers/act*_layer.py)
+
     ops.py           scatter_add, op_aggr, s_*_e_sum / s_*_e_mean (fused HIP), s_*_e, s_*_t   (cogdl/operators/ops.py)
 
 Submodules are imported lazily: GPU modules load libcogdl_hip.so at import and raise if it
@@ -119,4 +124,8 @@ def __getattr__(name):
         from . import multiplex
 
         return multiplex.multiplex_embed
+    if name in ("quantize", "dequantize", "relu_packed", "dropout_regen", "linear_q", "Quantized"):
+        from . import actq
+
+        return getattr(actq, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

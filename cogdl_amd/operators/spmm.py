@@ -10,7 +10,9 @@ Differences from the reference, all deliberate (SURVEY.md section 7 "hard parts"
     truly symmetric weighted graph -- for those both give the same operator.
   * unweighted + not sym no longer calls csr2csc(None) (operators/spmm.py:75).
   * failures raise BackendError instead of silently falling back to torch.scatter_add.
-  * actnn=True (activation quantisation, third_party/actnn absent) is rejected loudly.
+  * actnn=True with an edge weight that requires a gradient saves the dense operand quantised (ActSPMMFunction, the law of
+    csrc/actq_law.h at cogdl_amd.actnn_compat.config's bits and group size) and dequantises it for the SDDMM of the backward;
+    otherwise it is exactly actnn=False, as in the reference.  With an int64 `rowptr` it raises.
   * an int64 `rowptr` (with int32 `colind`) selects the 64-bit CSR path (cogdl_amd/bigcsr.py): graphs of 2^31 edges
     and more, which the reference's `.int()` cast cannot express.
 """
@@ -265,64 +267,75 @@ class SPMMFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rowptr, colind, feat, edge_weight_csr=None, sym=False):
-        # The structure hash is enqueued BEFORE the SpMM so that it has landed in pinned host memory long
-        # before backward asks for it (Fingerprint.key() waits on an event recorded right behind the hash
-        # kernel, not behind the SpMM).
-        rowptr, colind = _lib.csr_structure(rowptr, colind)  # validated + contiguous before anything reads raw pointers
-        ctx.transient = _plan.transient()  # (the dense operand is checked by csr_spmm_raw)
-        if ctx.transient:
-            ctx.fp = None
-        elif ctx.needs_input_grad[2] or _plan.memoised(rowptr) or _plan.taping():
-            ctx.fp = fingerprint_of(rowptr, colind, feat.shape[0])
-        else:
-            ctx.fp = _plan.known_fingerprint(rowptr, colind, feat.shape[0])  # (never hashes: inference calls stay as they were)
-        ctx.xcd, xplan = xcdplan.spmm_forward(ctx.fp, rowptr, colind, feat)
-        fwd_sweep = xcdplan.spmm_forward_sweep(ctx.fp, rowptr, colind, feat) if xplan is None else None
-        if xplan is not None:
-            out = csr_spmm_xcd_raw(xplan, edge_weight_csr, feat)
-        elif fwd_sweep is not None:
-            # a structure of this shape came back before and left its forward layout: both launches go out, guarded by the hash
-            # that is in flight, and the device runs the one that fits (no wait, same bits either way)
-            out = csr_spmm_sweep_forward_raw(fwd_sweep, ctx.fp.dev, rowptr, colind, edge_weight_csr, feat)
-        else:
-            out = csr_spmm_raw(rowptr, colind, edge_weight_csr, feat)
-        need_w = edge_weight_csr is not None and ctx.needs_input_grad[3]
-        ctx.n_src = feat.shape[0]
-        ctx.sym = sym
+        out, rowptr, colind, need_w = _spmm_forward(ctx, rowptr, colind, feat, edge_weight_csr, sym)
         ctx.save_for_backward(rowptr, colind, edge_weight_csr, feat if need_w else None)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         rowptr, colind, w, feat = ctx.saved_tensors
-        grad_out = grad_out.contiguous()
-        grad_feat = grad_w = None
-        if ctx.needs_input_grad[2]:
-            if ctx.transient:  # (plan.transient_structures: a one-off structure, transposed here, nothing cached or read back)
-                plan = csr2csc(rowptr, colind, ctx.n_src, padded=True)
-                w_t = gather_rows(plan.perm, w.detach()) if w is not None else None
-                grad_feat = csr_spmm_raw(plan.colptr, plan.rowind, w_t, grad_out)
-            else:
-                plan = PLANS.get(ctx.fp, rowptr, colind, ctx.n_src)
-                if plan.sightings > 1 and ctx.xcd is None and xcdplan.spmm_forward_sweep_shape(
-                        plan.m, plan.nnz, ctx.n_src, grad_out.shape[1], grad_out.dtype):
-                    # a structure that comes back, of a shape whose FORWARD may walk a sweep layout: build it (once) and make
-                    # the structure the candidate later forward calls of this shape speculate on
-                    from .. import sweepplan
+        return _spmm_backward(ctx, rowptr, colind, w, feat, grad_out)
 
-                    sweepplan.register_forward(ctx.fp, rowptr, colind, grad_out.shape[1], grad_out.dtype)
-                split_t, xplan_t = xcdplan.spmm_backward(ctx.fp, plan, grad_out, ctx.xcd is not None)
-                if split_t is not None:
-                    # (w stays in CSR order: the plan of the transpose maps its positions through the transpose's perm)
-                    grad_feat = csr_spmm_xcd_raw(xplan_t, w, grad_out)
-                elif xcdplan.spmm_backward_sweep(plan, grad_out):
-                    grad_feat = csr_spmm_sweep_raw(plan, w, grad_out)  # (w stays in CSR order: the layout composes the perm)
-                else:
-                    w_t = plan.transposed_values(w) if w is not None else None
-                    grad_feat = csr_spmm_raw(plan.colptr, plan.rowind, w_t, grad_out, split_long_rows=plan.has_hub_columns())
-        if w is not None and ctx.needs_input_grad[3]:
-            grad_w = csr_sddmm_raw(rowptr, colind, grad_out, feat.detach()).to(w.dtype)
-        return None, None, grad_feat, grad_w, None
+
+def _spmm_forward(ctx, rowptr, colind, feat, edge_weight_csr, sym):
+    """SPMMFunction's forward up to what it saves: -> (out, rowptr, colind as launched, "the backward needs feat")."""
+    # The structure hash is enqueued BEFORE the SpMM so that it has landed in pinned host memory long
+    # before backward asks for it (Fingerprint.key() waits on an event recorded right behind the hash
+    # kernel, not behind the SpMM).
+    rowptr, colind = _lib.csr_structure(rowptr, colind)  # validated + contiguous before anything reads raw pointers
+    ctx.transient = _plan.transient()  # (the dense operand is checked by csr_spmm_raw)
+    if ctx.transient:
+        ctx.fp = None
+    elif ctx.needs_input_grad[2] or _plan.memoised(rowptr) or _plan.taping():
+        ctx.fp = fingerprint_of(rowptr, colind, feat.shape[0])
+    else:
+        ctx.fp = _plan.known_fingerprint(rowptr, colind, feat.shape[0])  # (never hashes: inference calls stay as they were)
+    ctx.xcd, xplan = xcdplan.spmm_forward(ctx.fp, rowptr, colind, feat)
+    fwd_sweep = xcdplan.spmm_forward_sweep(ctx.fp, rowptr, colind, feat) if xplan is None else None
+    if xplan is not None:
+        out = csr_spmm_xcd_raw(xplan, edge_weight_csr, feat)
+    elif fwd_sweep is not None:
+        # a structure of this shape came back before and left its forward layout: both launches go out, guarded by the hash
+        # that is in flight, and the device runs the one that fits (no wait, same bits either way)
+        out = csr_spmm_sweep_forward_raw(fwd_sweep, ctx.fp.dev, rowptr, colind, edge_weight_csr, feat)
+    else:
+        out = csr_spmm_raw(rowptr, colind, edge_weight_csr, feat)
+    need_w = edge_weight_csr is not None and ctx.needs_input_grad[3]
+    ctx.n_src = feat.shape[0]
+    ctx.sym = sym
+    return out, rowptr, colind, need_w
+
+
+def _spmm_backward(ctx, rowptr, colind, w, feat, grad_out):
+    """SPMMFunction's backward from what it saved (feat: the dense operand, or None where no edge gradient is asked for)."""
+    grad_out = grad_out.contiguous()
+    grad_feat = grad_w = None
+    if ctx.needs_input_grad[2]:
+        if ctx.transient:  # (plan.transient_structures: a one-off structure, transposed here, nothing cached or read back)
+            plan = csr2csc(rowptr, colind, ctx.n_src, padded=True)
+            w_t = gather_rows(plan.perm, w.detach()) if w is not None else None
+            grad_feat = csr_spmm_raw(plan.colptr, plan.rowind, w_t, grad_out)
+        else:
+            plan = PLANS.get(ctx.fp, rowptr, colind, ctx.n_src)
+            if plan.sightings > 1 and ctx.xcd is None and xcdplan.spmm_forward_sweep_shape(
+                    plan.m, plan.nnz, ctx.n_src, grad_out.shape[1], grad_out.dtype):
+                # a structure that comes back, of a shape whose FORWARD may walk a sweep layout: build it (once) and make
+                # the structure the candidate later forward calls of this shape speculate on
+                from .. import sweepplan
+
+                sweepplan.register_forward(ctx.fp, rowptr, colind, grad_out.shape[1], grad_out.dtype)
+            split_t, xplan_t = xcdplan.spmm_backward(ctx.fp, plan, grad_out, ctx.xcd is not None)
+            if split_t is not None:
+                # (w stays in CSR order: the plan of the transpose maps its positions through the transpose's perm)
+                grad_feat = csr_spmm_xcd_raw(xplan_t, w, grad_out)
+            elif xcdplan.spmm_backward_sweep(plan, grad_out):
+                grad_feat = csr_spmm_sweep_raw(plan, w, grad_out)  # (w stays in CSR order: the layout composes the perm)
+            else:
+                w_t = plan.transposed_values(w) if w is not None else None
+                grad_feat = csr_spmm_raw(plan.colptr, plan.rowind, w_t, grad_out, split_long_rows=plan.has_hub_columns())
+    if w is not None and ctx.needs_input_grad[3]:
+        grad_w = csr_sddmm_raw(rowptr, colind, grad_out, feat.detach()).to(w.dtype)
+    return None, None, grad_feat, grad_w, None
 
 
 def csr_spmm_epilogue_raw(rowptr, colind, val, x, src_scale=None, dst_scale=None, bias=None, relu=False,
@@ -431,10 +444,41 @@ def csrspmm_block(rowptr, colind, x, csr_data=None, in_norm=None, max_row_edges=
     return FusedSPMMFunction.apply(rowptr, colind, x, csr_data, None, in_norm, None, False, True, max_row_edges)
 
 
+class ActSPMMFunction(torch.autograd.Function):
+    """Mirrors cogdl.operators.spmm.ActSPMMFunction (operators/spmm.py:89-133): SPMMFunction whose dense operand is saved
+    quantised (operators/actq.py, at the bits and group size of cogdl_amd.actnn_compat.config) for the edge-weight gradient.
+    out and grad_feat are SPMMFunction's bit for bit; grad_edge_weight is the SDDMM against the dequantised operand."""
+
+    @staticmethod
+    def forward(ctx, rowptr, colind, feat, edge_weight_csr=None, sym=False):
+        from .. import actnn_compat
+        from . import actq
+
+        out, rowptr, colind, need_w = _spmm_forward(ctx, rowptr, colind, feat, edge_weight_csr, sym)
+        ctx.q = actq.quantize(feat, actnn_compat.config.bits, actnn_compat.config.group_size) if need_w else None
+        ctx.feat_shape = tuple(feat.shape)
+        ctx.save_for_backward(rowptr, colind, edge_weight_csr)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from . import actq
+
+        rowptr, colind, w = ctx.saved_tensors
+        feat = None
+        if ctx.q is not None and ctx.needs_input_grad[3]:
+            feat = actq.dequantize(ctx.q, ctx.feat_shape)  # transient: gone when this function returns
+            ctx.q = None
+        return _spmm_backward(ctx, rowptr, colind, w, feat, grad_out)
+
+
 def csrspmm(rowptr, colind, x, csr_data, sym=False, actnn=False):
-    if actnn:
-        raise _lib.BackendError("actnn=True needs the ActNN quantiser (third_party/actnn is an empty submodule "
-                                "in the reference); not supported by the HIP backend")
+    if actnn and rowptr.dtype == torch.int64:
+        raise _lib.BackendError("actnn=True is not served on the 64-bit CSR path (an int64 rowptr): BigSPMMFunction saves the "
+                                "dense operand as it is; pass actnn=False, or an int32 rowptr")
+    if actnn and csr_data is not None and csr_data.requires_grad:
+        # (otherwise nothing dense is saved at all -- the reference's ActSPMMFunction saves nothing in that case either)
+        return ActSPMMFunction.apply(rowptr, colind, x, csr_data, sym)
     if rowptr.dtype == torch.int64:
         # 64-bit CSR (cogdl_amd/bigcsr.py): `graph.row_indptr` itself instead of `.int()` -- the only way to express a
         # graph of 2^31 edges or more (the reference's cast wraps, cogdl/utils/spmm_utils.py:106)

@@ -1371,6 +1371,32 @@ COGDL_API int cogdl_hip_multiplex_bwd_node(const float *g_y, const int32_t *occ_
 COGDL_API int cogdl_hip_multiplex_bwd_type(const float *g_c, const int32_t *occ_ptr, const int32_t *occ_pos, int64_t pos_base,
                        int64_t P, int64_t B, int64_t N, int64_t T, int64_t S, int64_t U, float *g_type, void *stream);
 
+/* -------------------------------------------------------------------------------------------------------------------
+ * Activation compression (added within ABI v9: new symbols only; csrc/actq.hip): what a layer saves for its backward pass,
+ * held in 1 / 2 / 4 / 8 bits per element, one bit per element, or not at all.  The law -- groups of the flattened tensor,
+ * bounds, Philox draws, stochastic rounding, packing, what a NaN / an infinity / an overflowing range does, the error bound
+ * -- is csrc/actq_law.h; the host twins (cogdl_host_<same name>, include/cogdl_host.h) return the same bytes.
+ *   cogdl_hip_actq_quantize    x fp32 [n] -> codes uint32 [ceil(n bits / 32)], meta fp32 [2 ceil(n / group)] ((mn, step) per
+ *                              group).  bits in {1, 2, 4, 8}, group in {64, 128, 256}; (seed, call) select the draws.
+ *   cogdl_hip_actq_dequantize  out[i] = mn + code * step, fp32 [n].
+ *   cogdl_hip_relu_mask        y = relu(x) (NaN kept), mask uint64 [ceil(n / 64)]: bit i % 64 of word i / 64 is x[i] > 0.
+ *   cogdl_hip_mask_apply       out[i] = bit i ? g[i] : 0.
+ *   cogdl_hip_drop_apply       y[i] = keep(seed, call, i) ? x[i] * scale : 0 with thresh in [0, 65536] (drop_params of
+ *                              csrc/philox.h); forward and backward are this one function.
+ * n == 0: success, nothing launched; n < 0, n >= 2^59, other bits / group / thresh, a NULL operand: COGDL_HIP_EINVAL.  fp32
+ * operands at any 4-byte boundary (16-byte aligned ones take 16-byte lanes, same results), meta and mask 8-byte aligned
+ * (COGDL_HIP_EALIGN otherwise).  Input and output must not overlap.  Stream-ordered, allocate nothing, do not synchronise; no
+ * atomics: results are equal from run to run and do not depend on the launch geometry.
+ * ------------------------------------------------------------------------------------------------------------------- */
+COGDL_API int cogdl_hip_actq_quantize(const float *x, int64_t n, int bits, int group, uint64_t seed, uint64_t call,
+                       uint32_t *codes, float *meta, void *stream);
+COGDL_API int cogdl_hip_actq_dequantize(const uint32_t *codes, const float *meta, int64_t n, int bits, int group, float *out,
+                       void *stream);
+COGDL_API int cogdl_hip_relu_mask(const float *x, int64_t n, float *y, uint64_t *mask, void *stream);
+COGDL_API int cogdl_hip_mask_apply(const float *g, const uint64_t *mask, int64_t n, float *out, void *stream);
+COGDL_API int cogdl_hip_drop_apply(const float *x, int64_t n, uint64_t seed, uint64_t call, uint32_t thresh, float scale,
+                       float *y, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -251,6 +251,19 @@ COGDL_HOST_API int cogdl_host_line_train(const int64_t *eu, const int64_t *ev, c
                                          int64_t S, double alpha, uint64_t seed, int workers, float *emb, float *ctx,
                                          int *flags, double *trace, int64_t trace_cap, int64_t *trace_n);
 
+/* Activation compression; the host twins of cogdl_hip_actq_quantize / _actq_dequantize / _relu_mask / _mask_apply /
+ * _drop_apply (include/cogdl_hip.h, where the contract is spelled out): same arguments minus the stream, all pointers host
+ * memory, no alignment requirement.  Both sides follow csrc/actq_law.h, so for equal inputs every output byte is the GPU's.
+ * OpenMP over tiles of 256 elements; the result does not depend on the number of threads. */
+COGDL_HOST_API int cogdl_host_actq_quantize(const float *x, int64_t n, int bits, int group, uint64_t seed, uint64_t call,
+                                            uint32_t *codes, float *meta);
+COGDL_HOST_API int cogdl_host_actq_dequantize(const uint32_t *codes, const float *meta, int64_t n, int bits, int group,
+                                              float *out);
+COGDL_HOST_API int cogdl_host_relu_mask(const float *x, int64_t n, float *y, uint64_t *mask);
+COGDL_HOST_API int cogdl_host_mask_apply(const float *g, const uint64_t *mask, int64_t n, float *out);
+COGDL_HOST_API int cogdl_host_drop_apply(const float *x, int64_t n, uint64_t seed, uint64_t call, uint32_t thresh, float scale,
+                                         float *y);
+
 #ifdef __cplusplus
 }
 #endif
