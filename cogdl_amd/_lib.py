@@ -210,6 +210,12 @@ HIP_SIGNATURES = {
     "cogdl_hip_relu_mask": ([_vp, _i64, _vp, _vp, _vp], _i32),
     "cogdl_hip_mask_apply": ([_vp, _vp, _i64, _vp, _vp], _i32),
     "cogdl_hip_drop_apply": ([_vp, _i64, _u64, _u64, _u32, _f32, _vp, _vp], _i32),
+    # HIN2Vec pair building and scoring (csrc/hin2vec.hip)
+    "cogdl_hip_hin_pairs_scratch_words": ([_i64], _i64),
+    "cogdl_hip_hin_pairs_count": ([_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp], _i32),
+    "cogdl_hip_hin_pairs_emit": ([_vp, _i64, _i64, _i32, _i64] + [_vp] * 4 + [_i64, _u64, _vp, _i64] + [_vp] * 6, _i32),
+    "cogdl_hip_hin_score": ([_vp] * 5 + [_i64] * 4 + [_vp, _vp], _i32),
+    "cogdl_hip_hin_score_grad": ([_vp] * 10 + [_i64] * 4 + [_i32, _vp, _vp, _i64, _vp], _i32),
 }
 
 MAX_SEGMENTS = 64  # COGDL_HIP_MAX_SEGMENTS
@@ -263,6 +269,8 @@ HOST_SIGNATURES = {
     "cogdl_host_relu_mask": ([_vp, _i64, _vp, _vp], _i32),
     "cogdl_host_mask_apply": ([_vp, _vp, _i64, _vp], _i32),
     "cogdl_host_drop_apply": ([_vp, _i64, _u64, _u64, _u32, _f32, _vp], _i32),
+    "cogdl_host_hin_pairs_count": ([_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp], _i32),
+    "cogdl_host_hin_pairs_emit": ([_vp, _i64, _i64, _i32, _i64] + [_vp] * 4 + [_i64, _u64, _vp, _i64] + [_vp] * 5, _i32),
 }
 
 EUNSUPPORTED = 7  # COGDL_HIP_EUNSUPPORTED

@@ -10,6 +10,7 @@ library's skip-gram operator -- what the reference's DeepWalk / Node2vec do thro
     graph2vec(graphs, dim, rounds, min_count, epochs)                       -> float32 [G, dim]  (one row per graph)
     line(graph_or_csr, dim, walk_length, walk_num, negative, alpha, order)  -> float32 [N, dim]
     gatne(layers, dim, walk_length, walk_num, window, epochs, batch_size, ...) -> (float32 [T, N, dim], nodes int64 [N])
+    hin2vec(graph_or_csr, node_type, dim, walk_length, walk_num, batch_size, hop, negative, epochs, lr) -> float32 [N, dim]
 
 `graph_or_csr` is a cogdl Graph (its row_indptr / col_indices are used on the device they live on) or an
 (indptr, indices) pair of int64 tensors.  Each of the walk_num passes starts one walk at every node, in an order shuffled
@@ -24,6 +25,9 @@ matrix, the sparsifier's log transform, a randomized SVD -- all three from cogdl
 prone is the other one (cogdl/models/emb/prone.py): an elementwise transform of the adjacency's entries, the same randomized
 SVD, the spectral propagation of cogdl_amd/operators/spectral.py (one fused filter step per sparse product) and a dense
 embedding from the [dim, dim] Gram matrix.
+
+hin2vec (cogdl/models/emb/hin2vec.py) is the typed-pair member: uniform walks cut at a dead end, the training rows of
+cogdl_amd/operators/hin2vec.py's hin_pairs, and Adam steps on its hin_scores.
 
 line is the edge-sampling member (cogdl/models/emb/line.py): no walks, walk_length * walk_num * N edge samples trained by
 cogdl_amd/operators/line.py, orders 1 and 2 side by side for order 3.
@@ -542,3 +546,44 @@ def line(graph_or_csr, dim=128, walk_length=80, walk_num=20, negative=5, alpha=0
     edges, weight = undirected_edges(row, indices, n, edge_weight)
     return line_from_edges(edges, n, weight, dim=dim, samples=int(walk_length) * int(walk_num) * n, negative=negative, alpha=alpha,
                            order=order, seed=seed, workers=workers)
+
+
+def hin2vec(graph_or_csr, node_type, dim=128, walk_length=80, walk_num=40, batch_size=1000, hop=2, negative=5, epochs=1, lr=0.025,
+            seed=None):
+    """HIN2Vec (cogdl/models/emb/hin2vec.py:173-220) -> float32 [N, dim] on the graph's device.  Each of the walk_num passes
+    starts one uniform walk at every node (random_walk); a walk that reaches a node without out-neighbours is cut there, as
+    the reference's walk breaks: the positions behind the first dead end become -1.  The rows (x, y, key, label) come from
+    hin_pairs, r is the dense rank of key (torch.unique).  Training is the reference's: Wx, Wr ~ randn, torch.optim.Adam(lr),
+    consecutive batches of batch_size rows with the trailing partial batch dropped, and the loss
+    CrossEntropyLoss()(stack([p, 1 - p], 1), label) exactly as the reference writes it (p and 1 - p used as logits), with p
+    from hin_scores.  The reference's per-batch loss.item() and accuracy bookkeeping are not reproduced.  `seed` makes a run
+    reproducible on one device."""
+    from .operators.hin2vec import hin_pairs, hin_scores
+
+    walk_num, walk_length, batch_size, epochs, dim = int(walk_num), int(walk_length), int(batch_size), int(epochs), int(dim)
+    if min(walk_num, batch_size, dim) < 1 or epochs < 0:
+        raise ValueError("hin2vec: walk_num, batch_size and dim must be at least 1, epochs at least 0")
+    indptr, indices = _csr(graph_or_csr)
+    dev, n = indptr.device, indptr.numel() - 1
+    node_type = torch.as_tensor(node_type).to(dev)
+    if node_type.dim() != 1 or node_type.numel() != n or node_type.dtype not in (torch.int32, torch.long):
+        raise ValueError("hin2vec: node_type must be an integer tensor with one entry per node (%d)" % n)
+    seed = _seed(seed)
+    walks = random_walk(indptr, indices, _starts(n, walk_num, seed, dev), walk_length, seed=(seed + 1) & (2 ** 64 - 1))
+    dead = (indptr[1:] == indptr[:-1])[walks]
+    walks = walks.masked_fill((torch.cumsum(dead, 1) - dead.long()) > 0, -1)
+    x, y, key, label = hin_pairs(walks, node_type, hop, negative, seed=(seed + 2) & (2 ** 64 - 1))
+    relations, r = torch.unique(key, return_inverse=True)
+    gen = torch.Generator(device=dev).manual_seed((seed + 3) % (2 ** 63))
+    Wx = torch.randn((n, dim), generator=gen, dtype=torch.float32, device=dev).requires_grad_()
+    Wr = torch.randn((max(relations.numel(), 1), dim), generator=gen, dtype=torch.float32, device=dev).requires_grad_()
+    opt = torch.optim.Adam([Wx, Wr], lr=lr)
+    criterion = torch.nn.CrossEntropyLoss()
+    for _ in range(epochs):
+        for lo in range(0, x.numel() - batch_size + 1, batch_size):
+            rows = slice(lo, lo + batch_size)
+            opt.zero_grad(set_to_none=True)
+            p = hin_scores(Wx, Wr, x[rows], y[rows], r[rows], check=False)  # (every id comes from this function's own tables)
+            criterion(torch.stack([p, 1 - p], dim=1), label[rows]).backward()
+            opt.step()
+    return Wx.detach()

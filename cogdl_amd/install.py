@@ -41,7 +41,7 @@ _finder = None
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
             metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False, readout=False,
             relational=False, genconv=False, disengcn=False, contrast=False, netsmf=False, metapath=False, prone=False,
-            kg_eval=False, kg_train=False, graph2vec=False, kg_sample=False, gatne=False, actnn=False, line=False):
+            kg_eval=False, kg_train=False, graph2vec=False, kg_sample=False, hin2vec=False, gatne=False, actnn=False, line=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -218,6 +218,16 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     the flattened tensor, float32 (min, step) pairs, Philox draws keyed by torch.initial_seed(), float32 compute only, and
     the optimisation levels L3 and above are served as L2 with one warning.  A training step that uses it must not be
     captured in a graph (a replay would repeat one noise draw).
+    hin2vec=True rebinds Hin2vec.forward in cogdl.models.emb.hin2vec (opt-in: the draws are Philox's, not `random`'s and
+    numpy's; relation ids are the dense ranks of the type sequence, where the reference's `relation[meta_str] = len(meta_str)`
+    gives every path of one string length one id and can index past Wr; `cpu=True` is honoured by keeping everything on the
+    CPU) to cogdl_amd.hin2vec_compat: cogdl_amd.embedding.hin2vec walks the DiGraph with the library's random_walk, builds the
+    rows with hin_pairs and trains with one hin_scores call per batch (HIP kernels for CUDA tensors: no [N, N] one-hot
+    matrix, no [B, N] x [N, d] product, no float atomic; the host twin and the torch composition on the CPU) under
+    torch.optim.Adam(lr) with the reference's loss; the return value is the reference's (float32 numpy [num_node, hidden]).
+    Node ids that are not exactly 0 .. N-1 all occurring in an edge, a data.pos that is not an integer list of types in
+    [0, 64) covering every node, hop > 8, walk_length <= hop and a graph without edges reach the reference's forward
+    (INTEGRATION.md).
     linear=True additionally routes torch.nn.functional.linear -- i.e. the unchanged nn.Linear inside every CogDL
     layer -- through cogdl_amd.linear (hand-written MFMA weight gradient for full-graph shapes)."""
     global _finder
@@ -372,6 +382,12 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
         _import_target(gatne_compat._MODULE, "gatne")
         if not gatne_compat.install():
             raise _lib_error("install(gatne=True): GATNE.forward could not be rebound")
+    if hin2vec:
+        from . import hin2vec_compat
+
+        _import_target(hin2vec_compat._MODULE, "hin2vec")
+        if not hin2vec_compat.install():
+            raise _lib_error("install(hin2vec=True): Hin2vec.forward could not be rebound")
     su =sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):

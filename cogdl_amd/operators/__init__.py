@@ -48,6 +48,9 @@
                                                                         operators/linear.py, operators/spmm.py:89-133,
                                                                         layers/act*_layer.py)
 
+    hin2vec.py       hin_pairs, hin_scores (also exported here)        (RWgraph.data_preparation and Hin2vec_layer.forward,
+                                                                        models/emb/hin2vec.py:36-48,84-117)
+
     ops.py           scatter_add, op_aggr, s_*_e_sum / s_*_e_mean (fused HIP), s_*_e, s_*_t   (cogdl/operators/ops.py)
 
 Submodules are imported lazily: GPU modules load libcogdl_hip.so at import and raise if it
@@ -128,4 +131,8 @@ def __getattr__(name):
         from . import actq
 
         return getattr(actq, name)
+    if name in ("hin_pairs", "hin_scores"):
+        from . import hin2vec
+
+        return getattr(hin2vec, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -1397,6 +1397,42 @@ COGDL_API int cogdl_hip_mask_apply(const float *g, const uint64_t *mask, int64_t
 COGDL_API int cogdl_hip_drop_apply(const float *x, int64_t n, uint64_t seed, uint64_t call, uint32_t thresh, float scale,
                        float *y, void *stream);
 
+/* -------------------------------------------------------------------------------------------------------------------
+ * HIN2Vec (added within ABI v9: new symbols only; csrc/hin2vec.hip): the training rows of typed walks and the score of a
+ * batch with its two gradients.  Slots, keys, draws, the order of every sum: csrc/hin2vec_law.h.
+ *   cogdl_hip_hin_pairs_scratch_words  int64 words of scratch cogdl_hip_hin_pairs_count needs for W walks (0 for small W).
+ *   cogdl_hip_hin_pairs_count   walks int64 [W, L] (-1 from a walk's end on), hop in [1, 8], L > hop, node_type int32 [N] in
+ *                               [0, 64) -> offsets int64 [W + 1]: the number of live slots before walk w, offsets[W] their
+ *                               total.  Clears *flags and raises 1 (a node id outside [0, N)), 2 (a type outside [0, 64)),
+ *                               4 (a -1 that is not in a suffix).
+ *   cogdl_hip_hin_pairs_emit    offsets as counted, total = offsets[W] -> x, y, key, label int64 [total (1 + negative)]: per
+ *                               live slot in slot order the positive row and its negatives.  type_ptr int32 [65], type_nodes
+ *                               and rank int32 [N]: the nodes grouped by type and a node's place in its group.  Raises 8 into
+ *                               *flags (not cleared) where a group cannot give a replacement.
+ *   cogdl_hip_hin_score         p[b] = sigmoid(SUM_k Wx[x_b, k] Wx[y_b, k] f(Wr[r_b, k])), fp32 [B]; Wx [N, D], Wr [R, D],
+ *                               x, y, r int32 [B].  An id outside its table scores NaN.  D <= 16384.
+ *   cogdl_hip_hin_score_grad    relation == 0: grad = dL/dWx [N, D] from the inverted index of (x_0 .. x_{B-1}, y_0 .. y_{B-1});
+ *                               relation == 1: grad = dL/dWr [R, D] from that of r.  occ_ptr int32 [rows + 1], occ_pos the
+ *                               positions ascending inside a row, chunk_ptr int32 [rows + 1] = the running sum of
+ *                               max(1, ceil(occurrences / 512)); partials fp32 [partial_rows, D] with partial_rows >=
+ *                               occurrences / 512.  Every row of grad is written, zeros included.
+ * The host twins of the pair builder (cogdl_host_hin_pairs_count / _emit) return the same bytes; the score has none.
+ * Stream-ordered, allocate nothing, do not synchronise; no atomics: results are equal from run to run.
+ * ------------------------------------------------------------------------------------------------------------------- */
+COGDL_API int64_t cogdl_hip_hin_pairs_scratch_words(int64_t W);
+COGDL_API int cogdl_hip_hin_pairs_count(const int64_t *walks, int64_t W, int64_t L, int hop, const int32_t *node_type, int64_t N,
+                       int64_t *offsets, int64_t *scratch, int *flags, void *stream);
+COGDL_API int cogdl_hip_hin_pairs_emit(const int64_t *walks, int64_t W, int64_t L, int hop, int64_t negative,
+                       const int32_t *node_type, const int32_t *type_ptr, const int32_t *type_nodes, const int32_t *rank,
+                       int64_t N, uint64_t seed, const int64_t *offsets, int64_t total, int64_t *x, int64_t *y, int64_t *key,
+                       int64_t *label, int *flags, void *stream);
+COGDL_API int cogdl_hip_hin_score(const float *Wx, const float *Wr, const int32_t *x, const int32_t *y, const int32_t *r,
+                       int64_t B, int64_t N, int64_t R, int64_t D, float *p, void *stream);
+COGDL_API int cogdl_hip_hin_score_grad(const float *Wx, const float *Wr, const int32_t *x, const int32_t *y, const int32_t *r,
+                       const float *p, const float *grad_p, const int32_t *occ_ptr, const int32_t *occ_pos,
+                       const int32_t *chunk_ptr, int64_t B, int64_t N, int64_t R, int64_t D, int relation, float *grad,
+                       float *partials, int64_t partial_rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -264,6 +264,17 @@ COGDL_HOST_API int cogdl_host_mask_apply(const float *g, const uint64_t *mask, i
 COGDL_HOST_API int cogdl_host_drop_apply(const float *x, int64_t n, uint64_t seed, uint64_t call, uint32_t thresh, float scale,
                                          float *y);
 
+/* HIN2Vec's training rows; the host twins of cogdl_hip_hin_pairs_count / _emit (include/cogdl_hip.h, where the contract is
+ * spelled out): same arguments minus the stream, all pointers host memory, `scratch` is not read.  Both sides follow
+ * csrc/hin2vec_law.h, so for equal inputs and seed every output element is the GPU's.  OpenMP over the walks; the result does
+ * not depend on the number of threads. */
+COGDL_HOST_API int cogdl_host_hin_pairs_count(const int64_t *walks, int64_t W, int64_t L, int hop, const int32_t *node_type,
+                                              int64_t N, int64_t *offsets, int64_t *scratch, int *flags);
+COGDL_HOST_API int cogdl_host_hin_pairs_emit(const int64_t *walks, int64_t W, int64_t L, int hop, int64_t negative,
+                                             const int32_t *node_type, const int32_t *type_ptr, const int32_t *type_nodes,
+                                             const int32_t *rank, int64_t N, uint64_t seed, const int64_t *offsets,
+                                             int64_t total, int64_t *x, int64_t *y, int64_t *key, int64_t *label, int *flags);
+
 #ifdef __cplusplus
 }
 #endif
