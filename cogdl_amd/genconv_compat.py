@@ -8,6 +8,8 @@ is an online softmax with the row maximum carried, so the sums are re-associated
 up to float32 rounding, not the same bits -- and large beta * m neither overflows nor goes through the halving loop of the
 reference's CPU softmax (cogdl/utils/spmm_utils.py:157-160).  `softmax_sg` uses the layer's beta parameter, `softmax` beta = 1,
 `mean` the reference's 1 / deg with 0 for an empty row, every other name the plain sum, as the reference's `else` branch.
+Under torch.autocast for the GPU the node features and the encoded edge term are cast to the autocast dtype for that one call,
+which then runs the operator's fp16 / bf16 kernels: fp32 arithmetic, one rounding where the output and each gradient is stored.
 
 What does not: the edge encoder, message_norm, the residual and the MLP are the reference's lines.  The reference's own forward
 (cogdl_amd/_rebind.original) is called
@@ -83,7 +85,16 @@ def forward(self, graph, x):
         aggr, beta = "softmax", None
     else:
         aggr, beta = ("mean" if self.aggr == "mean" else "sum"), None
-    h = gen_aggregate(x, row, col, eterm, aggr, beta, self.eps, num_nodes=x.shape[0])
+    xa = x
+    if x.is_cuda and torch.is_autocast_enabled():
+        # torch AMP (the Trainer's fp16=True): LayerNorm hands the layer fp32 while the edge encoder's Linear hands it the
+        # autocast dtype.  Both go to the operator in that dtype -- its 16-bit kernels -- and nowhere else: message_norm, the
+        # residual and the MLP see the x they were given, and the aggregate in x's dtype as on the reference's route (in fp16
+        # F.normalize's eps = 1e-12 is 0, and a node without in-edges would be 0 / 0).  Outside autocast nothing is cast.
+        cast = torch.get_autocast_gpu_dtype()
+        xa = x.to(cast)
+        eterm = None if eterm is None else eterm.to(cast)
+    h = gen_aggregate(xa, row, col, eterm, aggr, beta, self.eps, num_nodes=x.shape[0]).to(x.dtype)
     if self.use_msg_norm:
         h = self.message_norm(x, h)
     if self.residual:

@@ -100,8 +100,10 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     genconv=True rebinds GENConv.forward in cogdl.layers.deepergcn_layer (opt-in: no longer the unchanged layer, and the softmax
     sums are re-associated -- float32 rounding apart, the same numbers) to cogdl_amd.genconv_compat: the aggregation of the
     deepergcn and revgcn models (gather, edge encoder term, relu + eps, beta, per-column edge softmax, multiply, scatter_add_)
-    is one call of the library's gen_aggregate operator (HIP kernels for CUDA tensors: no [E, F] message tensors, no float
-    atomics, equal from run to run; the torch composition on the CPU).  `softmax_sg`, `softmax`, `mean` and the plain sum are
+    is one call of the library's gen_aggregate operator (HIP kernels for float32, float16 and bfloat16 CUDA tensors: no [E, F]
+    message tensors, no float atomics, equal from run to run; the torch composition on the CPU).  Under torch.autocast for
+    the GPU the node features and the encoded edge term are cast to the autocast dtype for that call: fp32 arithmetic, the
+    output and each gradient rounded once where it is stored.  `softmax_sg`, `softmax`, `mean` and the plain sum are
     served; `powermean`, `max`, a graph without a CSR and a graph whose CSR does not describe its edge_index reach the
     reference's forward.
     disengcn=True rebinds DisenGCNLayer.forward in cogdl.layers.disengcn_layer (opt-in: no longer the unchanged layer, and the

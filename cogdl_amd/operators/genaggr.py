@@ -21,9 +21,17 @@ of operators/ops.py (`edge_plan`); building them is also the range check of row 
 (beta, when a tensor, is read by the kernel through its address), so a later call on the same index tensors can be captured
 in a graph.
 
+fp16 / bf16 GPU tensors (x and eterm of one dtype: what the layer sees under torch AMP) go to the 16-bit entries of the same
+kernels (cogdl_hip_gen_aggr16_fwd / _bwd, csrc/genaggr16.hip): elements are converted where they are loaded, all arithmetic is
+the fp32 kernels', and out, grad_x and grad_eterm are rounded once where they are stored (an fp16 result beyond 65504 is inf).
+lse and q stay fp32, and the forward also keeps the output before its rounding (out32) for the backward and for the gradient of
+beta, sum(grad.float() * (q - out32^2)) in fp32.  beta is None, a float or a float32 tensor.  `mean` scales the upstream
+gradient per destination in fp32 and hands the kernel that fp32 tensor.
+
 CPU tensors run the torch composition: the same formula with a true per-row softmax, the row maximum subtracted.  A GPU call
-the kernel does not cover (other dtypes, tensors on several devices, F == 0, E == 0, an empty x or output) runs the same
-composition and says so once per reason with a TorchRouteWarning, as operators/ops.py does.
+the kernel does not cover (float64, x and eterm of different dtypes, a 16-bit beta tensor, tensors on several devices, F == 0,
+E == 0, an empty x or output) runs the same composition and says so once per reason with a TorchRouteWarning, as operators/ops.py
+does.
 """
 import torch
 
@@ -41,8 +49,9 @@ def _note_torch_route(why):
     _ROUTE_NOTED.add(("gen_aggregate", why))
     import warnings
 
-    warnings.warn("cogdl_amd.operators.genaggr.gen_aggregate: GPU tensors on the torch route (%s); the fused HIP kernel covers "
-                  "2-D float32 x and eterm with 1-D int64 row and col, all on one device" % why, TorchRouteWarning, stacklevel=3)
+    warnings.warn("cogdl_amd.operators.genaggr.gen_aggregate: GPU tensors on the torch route (%s); the fused HIP kernels cover "
+                  "2-D x and eterm that are both float32, float16 or bfloat16 (beta: None, a float or a float32 tensor) with 1-D int64 row "
+                  "and col, all on one device" % why, TorchRouteWarning, stacklevel=3)
 
 
 def _composition(x, row, col, eterm, aggr, beta, eps, num_nodes):
@@ -84,19 +93,30 @@ class _GenAggregate(torch.autograd.Function):
         softmax = aggr == "softmax"
         want_beta = softmax and beta_t is not None and ctx.needs_input_grad[2]
         want_bwd = any(ctx.needs_input_grad[:3])
-        out = torch.empty((num_nodes, k), dtype=torch.float32, device=dev)
-        lse = torch.empty_like(out) if softmax and want_bwd else None
-        q = torch.empty_like(out) if want_beta else None
-        ws, ws_bytes = _lib.workspace("cogdl_hip_gen_aggr_fwd_workspace_bytes", dev, nnz, k)
+        half = x.dtype != torch.float32
+        out = torch.empty((num_nodes, k), dtype=x.dtype, device=dev)
+        lse = torch.empty((num_nodes, k), dtype=torch.float32, device=dev) if softmax and want_bwd else None
+        q = torch.empty_like(lse) if want_beta else None
+        out32 = torch.empty_like(lse) if half and lse is not None else None  # the output before its rounding: for the backward
         eid = None if dplan.sorted else dplan.perm
         bptr, bval = _beta_args(beta_t if softmax else None, beta_f)
-        with _lib.on_device(dev):
-            rc = _lib.hip().cogdl_hip_gen_aggr_fwd(_lib.ptr(dplan.rowptr), _lib.ptr(dplan.colind(col)), _lib.ptr(eid), _lib.ptr(x),
-                                                   _lib.ptr(eterm), _MODE[aggr], bptr, bval, eps, _lib.ptr(out), _lib.ptr(lse),
-                                                   _lib.ptr(q), num_nodes, k, nnz, _lib.ptr(ws), ws_bytes, _lib.stream_of(out))
+        if half:
+            code = _lib.DTYPE_CODE[x.dtype]
+            ws, ws_bytes = _lib.workspace("cogdl_hip_gen_aggr16_fwd_workspace_bytes", dev, nnz, k, code)
+            with _lib.on_device(dev):
+                rc = _lib.hip().cogdl_hip_gen_aggr16_fwd(_lib.ptr(dplan.rowptr), _lib.ptr(dplan.colind(col)), _lib.ptr(eid),
+                                                         _lib.ptr(x), _lib.ptr(eterm), _MODE[aggr], bptr, bval, eps, _lib.ptr(out),
+                                                         _lib.ptr(out32), _lib.ptr(lse), _lib.ptr(q), num_nodes, k, nnz, code,
+                                                         _lib.ptr(ws), ws_bytes, _lib.stream_of(out))
+        else:
+            ws, ws_bytes = _lib.workspace("cogdl_hip_gen_aggr_fwd_workspace_bytes", dev, nnz, k)
+            with _lib.on_device(dev):
+                rc = _lib.hip().cogdl_hip_gen_aggr_fwd(_lib.ptr(dplan.rowptr), _lib.ptr(dplan.colind(col)), _lib.ptr(eid), _lib.ptr(x),
+                                                       _lib.ptr(eterm), _MODE[aggr], bptr, bval, eps, _lib.ptr(out), _lib.ptr(lse),
+                                                       _lib.ptr(q), num_nodes, k, nnz, _lib.ptr(ws), ws_bytes, _lib.stream_of(out))
         _lib.check(rc, "gen_aggr_fwd")
         ctx.plans, ctx.aggr, ctx.beta_f, ctx.eps = (dplan, splan), aggr, beta_f, eps
-        ctx.save_for_backward(x, eterm, beta_t, row, out, lse, q)
+        ctx.save_for_backward(x, eterm, beta_t, row, out32 if half else out, lse, q)
         return out
 
     @staticmethod
@@ -104,33 +124,49 @@ class _GenAggregate(torch.autograd.Function):
     def backward(ctx, grad):
         x, eterm, beta_t, row, out, lse, q = ctx.saved_tensors
         dplan, splan = ctx.plans
-        if grad.dtype != torch.float32:
-            raise _lib.BackendError("gen_aggregate backward: grad must be float32 (got %s)" % grad.dtype)
+        if grad.dtype != x.dtype:
+            raise _lib.BackendError("gen_aggregate backward: grad must be %s (got %s)" % (str(x.dtype)[6:], grad.dtype))
         grad = grad.contiguous()
         softmax = ctx.aggr == "softmax"
         dev, k, nnz = x.device, x.shape[1], row.numel()
+        half = x.dtype != torch.float32
         g_x = g_t = g_beta = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             gs = grad
             if ctx.aggr == "mean":  # autograd's `grad[row] * deg_rev[row]`, one rounding: taken per destination, then gathered
                 inv = (dplan.rowptr[1:] - dplan.rowptr[:-1]).float().pow(-1)
-                gs = grad * torch.where(torch.isinf(inv), torch.zeros_like(inv), inv).view(-1, 1)
+                gs = grad.float() * torch.where(torch.isinf(inv), torch.zeros_like(inv), inv).view(-1, 1)  # (16-bit: stays fp32)
             g_x = torch.empty_like(x)
             if ctx.needs_input_grad[1]:
-                g_t = torch.empty((nnz, k), dtype=torch.float32, device=dev)
-            ws, ws_bytes = _lib.workspace("cogdl_hip_gen_aggr_bwd_workspace_bytes", dev, nnz, k)
+                g_t = torch.empty((nnz, k), dtype=x.dtype, device=dev)
             eid = None if splan.sorted else splan.perm
             bptr, bval = _beta_args(beta_t if softmax else None, ctx.beta_f)
-            with _lib.on_device(dev):
-                rc = _lib.hip().cogdl_hip_gen_aggr_bwd(_lib.ptr(splan.rowptr), _lib.ptr(splan.colind(row)), _lib.ptr(eid),
-                                                       _lib.ptr(x), _lib.ptr(eterm), _lib.ptr(gs), _lib.ptr(out), _lib.ptr(lse),
-                                                       _MODE[ctx.aggr], bptr, bval, ctx.eps, _lib.ptr(g_x), _lib.ptr(g_t),
-                                                       x.shape[0], k, nnz, _lib.ptr(ws), ws_bytes, _lib.stream_of(grad))
+            if half:
+                code = _lib.DTYPE_CODE[x.dtype]
+                ws, ws_bytes = _lib.workspace("cogdl_hip_gen_aggr16_bwd_workspace_bytes", dev, nnz, k, code)
+                with _lib.on_device(dev):
+                    rc = _lib.hip().cogdl_hip_gen_aggr16_bwd(_lib.ptr(splan.rowptr), _lib.ptr(splan.colind(row)), _lib.ptr(eid),
+                                                             _lib.ptr(x), _lib.ptr(eterm), _lib.ptr(gs), _lib.DTYPE_CODE[gs.dtype],
+                                                             _lib.ptr(out), _lib.ptr(lse), _MODE[ctx.aggr], bptr, bval, ctx.eps,
+                                                             _lib.ptr(g_x), _lib.ptr(g_t), x.shape[0], k, nnz, code, _lib.ptr(ws),
+                                                             ws_bytes, _lib.stream_of(grad))
+            else:
+                ws, ws_bytes = _lib.workspace("cogdl_hip_gen_aggr_bwd_workspace_bytes", dev, nnz, k)
+                with _lib.on_device(dev):
+                    rc = _lib.hip().cogdl_hip_gen_aggr_bwd(_lib.ptr(splan.rowptr), _lib.ptr(splan.colind(row)), _lib.ptr(eid),
+                                                           _lib.ptr(x), _lib.ptr(eterm), _lib.ptr(gs), _lib.ptr(out), _lib.ptr(lse),
+                                                           _MODE[ctx.aggr], bptr, bval, ctx.eps, _lib.ptr(g_x), _lib.ptr(g_t),
+                                                           x.shape[0], k, nnz, _lib.ptr(ws), ws_bytes, _lib.stream_of(grad))
             _lib.check(rc, "gen_aggr_bwd")
             if not ctx.needs_input_grad[0]:
                 g_x = None
         if q is not None and ctx.needs_input_grad[2]:
-            g_beta = (grad * (q - out * out)).sum().reshape(beta_t.shape)
+            var = q - out * out  # (16-bit: `out` is out32; fp32 throughout)
+            terms = grad.float() * var
+            if half:  # a 16-bit gradient may have overflowed where it does not matter: a row without edges (var is exactly 0, no
+                # edge gathers it) behind a normalisation whose fp32 gradient is ~1e12 there.  0 * inf is that row's 0, not nan.
+                terms = torch.where(var != 0, terms, torch.zeros_like(terms))
+            g_beta = terms.sum().reshape(beta_t.shape)
         return g_x, g_t, g_beta, None, None, None, None, None, None
 
 
@@ -164,10 +200,10 @@ def gen_aggregate(x, row, col, eterm=None, aggr="softmax", beta=None, eps=1e-7, 
     if not any(t.is_cuda for t in tensors):
         return _composition(x, row, col, eterm, aggr, beta_c, eps, num_nodes)  # the CPU route: quiet
     why = None
-    floats = (x,) + tuple(t for t in (eterm, beta_t) if t is not None)
     if not all(t.is_cuda and t.device == x.device for t in tensors):
         why = "tensors on %s" % sorted({str(t.device) for t in tensors})
-    elif not all(t.dtype == torch.float32 for t in floats):
+    elif not (x.dtype in _lib.DTYPE_CODE and (eterm is None or eterm.dtype == x.dtype)
+              and (beta_t is None or beta_t.dtype == torch.float32)):
         why = "x %s, eterm %s, beta %s" % (x.dtype, None if eterm is None else eterm.dtype, None if beta_t is None else beta_t.dtype)
     elif not (_is_index(row, e) and _is_index(col, e)):
         why = "row %s %s, col %s %s" % (row.dtype, tuple(row.shape), col.dtype, tuple(col.shape))

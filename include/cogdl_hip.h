@@ -522,6 +522,29 @@ COGDL_API int cogdl_hip_gen_aggr_bwd(const int32_t *srcptr, const int32_t *dst_s
                            const float *beta_dev, float beta, float eps, float *grad_x, float *grad_eterm, int64_t n_src,
                            int64_t k, int64_t nnz, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The same two passes on 16-bit tables (csrc/genaggr16.hip): dtype = COGDL_HIP_F16 | COGDL_HIP_BF16 (anything else:
+ * COGDL_HIP_EDTYPE) is the element type of x, eterm, out, grad_x and grad_eterm.  Elements are converted where they are loaded,
+ * all arithmetic -- the message, the online-softmax state, the merge of long-row pieces, the backward's term -- is the fp32
+ * arithmetic of the entries above, and each 16-bit result is rounded ONCE, to nearest, where it is stored (an fp16 result beyond
+ * 65504 becomes inf there; nothing is clamped).  lse and q stay fp32.
+ *   out32      [m, k] fp32, given exactly when lse is: the output before its rounding.  The backward reads this one, so that
+ *              1 + beta * (msg - out[v,:]) does not inherit the store's rounding.
+ *   grad       the upstream gradient; grad_dtype = dtype, or COGDL_HIP_F32 for SUM / MEAN (the caller's 1 / deg(v) scaling is
+ *              an fp32 product that is passed on as it is).
+ * The lane mapping is the fp32 entries' (vector width 4 -> 2 -> 1 by k and by the address of every table: tables that start anywhere
+ * on an element boundary are served).  Deterministic; a row of one edge returns msg rounded once, an empty row 0. */
+COGDL_API size_t cogdl_hip_gen_aggr16_fwd_workspace_bytes(int64_t nnz, int64_t k, int dtype);
+COGDL_API int cogdl_hip_gen_aggr16_fwd(const int32_t *rowptr, const int32_t *colind, const int32_t *eid, const void *x,
+                             const void *eterm, int mode, const float *beta_dev, float beta, float eps, void *out,
+                             float *out32, float *lse, float *q, int64_t m, int64_t k, int64_t nnz, int dtype,
+                             void *workspace, size_t workspace_bytes, void *stream);
+COGDL_API size_t cogdl_hip_gen_aggr16_bwd_workspace_bytes(int64_t nnz, int64_t k, int dtype);
+COGDL_API int cogdl_hip_gen_aggr16_bwd(const int32_t *srcptr, const int32_t *dst_sorted, const int32_t *eid, const void *x,
+                             const void *eterm, const void *grad, int grad_dtype, const float *out32, const float *lse,
+                             int mode, const float *beta_dev, float beta, float eps, void *grad_x, void *grad_eterm,
+                             int64_t n_src, int64_t k, int64_t nnz, int dtype, void *workspace, size_t workspace_bytes,
+                             void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Neighbourhood routing (csrc/disen.hip): one step of DisenGCN's routing loop (cogdl/layers/disengcn_layer.py:56-69) without
  * any [E, K d] or [E, K] tensor and without atomics.  c, z, out: [n, n_channels * d], channel k = columns k d .. (k + 1) d - 1.
