@@ -221,6 +221,11 @@ HIP_SIGNATURES = {
     "cogdl_hip_hin_pairs_emit": ([_vp, _i64, _i64, _i32, _i64] + [_vp] * 4 + [_i64, _u64, _vp, _i64] + [_vp] * 6, _i32),
     "cogdl_hip_hin_score": ([_vp] * 5 + [_i64] * 4 + [_vp, _vp], _i32),
     "cogdl_hip_hin_score_grad": ([_vp] * 10 + [_i64] * 4 + [_i32, _vp, _vp, _i64, _vp], _i32),
+    # pairwise log-sum-exp (csrc/contrast.hip)
+    "cogdl_hip_pair_lse_slices": ([_i64, _i64, _i64, _i32], _i64),
+    "cogdl_hip_pair_lse_workspace_bytes": ([_i64, _i64, _i64, _i64], _sz),
+    "cogdl_hip_pair_lse_fwd": ([_vp, _vp, _vp, _i64, _i64, _i64, _f32, _i64, _vp, _vp, _vp, _sz, _vp], _i32),
+    "cogdl_hip_pair_lse_grad": ([_vp] * 6 + [_i64, _i64, _i64, _f32, _i64, _i64, _vp, _vp, _vp, _sz, _vp], _i32),
 }
 
 MAX_SEGMENTS = 64  # COGDL_HIP_MAX_SEGMENTS

@@ -6,8 +6,10 @@ What changes: the two [N, N] float32 matrices exp(z1 z1^T / tau) and exp(z1 z2^T
 everything autograd keeps of them are one `grace_loss` call: the normalisation, then one operator that works in row blocks and
 recomputes the scores in its backward, so what it keeps is O(N d).  The diagonal term is left out of the row sum instead of being
 subtracted from it, and the sums go through logsumexp, so they are re-associated against the reference's: the same numbers up to
-float32 rounding, not the same bits -- and finite where the reference's plain exp overflows (tau below about 0.0113).  The
-operator is a torch composition: no HIP kernel serves it, on the GPU it runs torch's kernels (one TorchRouteWarning).
+float32 rounding, not the same bits -- and finite where the reference's plain exp overflows (tau below about 0.0113).  On
+float32 GPU tensors with d <= 256 grace_loss runs the streaming MFMA kernels of csrc/contrast.hip, except at the sizes where
+they measured slower than the blocked torch composition (profiles/contrast_bench.txt); everything else runs that composition,
+on the GPU with one TorchRouteWarning.
 
 What does not: `batched_loss` (lines 79-91) calls `self.contrastive_loss(z1[idx], z2)` and is served as it stands; `train_step`
 and everything else are the reference's.  Inputs that are not 2-D floating tensors of one width, dtype and device reach the

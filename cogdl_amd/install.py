@@ -116,9 +116,9 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     contrast=True rebinds GRACEModelWrapper.contrastive_loss in cogdl.wrappers.model_wrapper.node_classification.grace_mw (opt-in:
     no longer the unchanged wrapper, and the row sums are re-associated -- float32 rounding apart, the same numbers) to
     cogdl_amd.contrast_compat: the loss of the grace model is one call of the library's grace_loss (normalisation, then the
-    pair_lse operator: a torch composition in row blocks of the queries whose backward recomputes the scores, so neither of
-    the two [N, N] score matrices is kept; there is no HIP kernel behind it, GPU tensors run torch's kernels and say so once
-    with a TorchRouteWarning).  batched_loss calls the rebound method and is served as it stands.  Inputs that are not 2-D
+    pair_lse operator, whose backward recomputes the scores, so neither of the two [N, N] score matrices is kept: the streaming
+    MFMA kernels of csrc/contrast.hip for float32 GPU tensors with d <= 256 outside the sizes where they measured slower, a
+    torch composition in row blocks of the queries otherwise, on GPU tensors with one TorchRouteWarning).  batched_loss calls the rebound method and is served as it stands.  Inputs that are not 2-D
     float tensors of one width reach the reference's method.
     netsmf=True rebinds NetSMF.forward in cogdl.models.emb.netsmf (opt-in: the draws are Philox's, not numpy's; num_round rounds
     become ceil(num_round / 2) passes over the CSR entries, so an odd num_round is rounded up; a node without edges gets a zero

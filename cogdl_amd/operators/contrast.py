@@ -1,6 +1,6 @@
 """The row-wise log-sum-exp of a dense pairwise score matrix, and GRACE's contrastive loss on it.
 
-    pair_lse(q, k, tau, skip=None) -> lse [M]                                                (autograd: q, k)
+    pair_lse(q, k, tau, skip=None, *, block=None, route=None, split=None) -> lse [M]         (autograd: q, k)
         q [M, d], k [N, d]; skip None, or int32 / int64 [M] with entries in [-1, N) (-1: nothing skipped)
             lse[i] = log SUM_{j != skip[i]} exp(<q[i], k[j]> / tau)             an empty sum gives -inf
 
@@ -17,7 +17,14 @@ leaving j = i out of it -- which is what `skip` does, without the cancellation o
 F.normalize maps to zero.  batched_loss calls contrastive_loss(z1[idx], z2): the keys are then cat([a[idx], b]) with skip =
 arange(B), the reference's [B, B] plus [B, N] blocks.
 
-The operator is the torch composition -- matmul, the skipped entry masked to -inf, torch.logsumexp (the maximum subtracted: no
+Two routes compute it.  route="hip" (float32 CUDA tensors, d <= 256; what grace_loss picks for such inputs): the streaming MFMA
+kernels of csrc/contrast.hip -- score tiles of 64 x 64 from v_mfma_f32_32x32x2_f32, an online {max, sum} per query in the forward,
+the scores recomputed in two backward passes (one per gradient), no float atomics, nothing of size block x N; it keeps q, k,
+skip, lse and one more [M] vector (what lse * tau does not hold of the row's normaliser in float32).  d above 256 is not
+chunked: route="hip" raises BackendError there and grace_loss takes the torch route with its warning.  split= overrides the
+number of slices the walked side is cut into (tests).
+
+The torch route (route=None or "torch" in pair_lse) is the torch composition -- matmul, the skipped entry masked to -inf, torch.logsumexp (the maximum subtracted: no
 precondition on the size of the scores) -- evaluated in row blocks of the queries, forward AND backward: the forward keeps q,
 k, skip and lse only, and the backward recomputes every block's scores.  With p_ij = exp(<q_i, k_j> / tau - lse_i), 0 at j =
 skip[i], and g the upstream gradient:
@@ -25,9 +32,10 @@ skip[i], and g the upstream gradient:
     grad_q[i] = (g_i / tau) * SUM_j p_ij k[j]              grad_k[j] = (1 / tau) * SUM_i g_i p_ij q[i]
 
 So nothing of size [M, N] is kept and the working memory is a few tensors of block x N (`block` rows; by default as many as
-keep one of them near 64 MB).  There is NO HIP kernel behind this operator: CPU tensors run it quietly, GPU tensors run the
-same blocked composition on torch's kernels and say so once with a TorchRouteWarning, as operators/ops.py does.  A `skip`
-entry outside [-1, N) raises BackendError before anything is computed (one read-back of the tensor).
+keep one of them near 64 MB).  CPU tensors run it quietly, GPU tensors run the same blocked composition on torch's kernels and
+say so once with a TorchRouteWarning that names route="hip", as operators/ops.py does.  On either route a `skip` entry outside
+[-1, N) raises BackendError before anything is computed (one read-back of the tensor).  Which route is faster where:
+profiles/contrast_bench.txt (tools/contrast_bench.py), DESIGN.md.
 """
 import torch
 
@@ -112,10 +120,76 @@ def _check_skip(skip, m, n):
         raise _lib.BackendError("pair_lse: skip entries must lie in [-1, %d) (got %d .. %d)" % (n, lo, hi))
 
 
-def pair_lse(q, k, tau, skip=None, *, block=None, _skip_checked=False):
-    """q [M, d], k [N, d] -> lse [M] in the dtype of q.  block: query rows per step of the blocked composition.  BackendError
-    for arguments that are not 2-D floating tensors of one width and dtype, a tau that is not positive, and a skip of another
-    shape, dtype or range."""
+ROUTES = (None, "torch", "hip")
+HIP_MAX_D = 256  # the widest rows csrc/contrast.hip keeps in LDS; wider rows are the torch route's
+# grace_loss(route=None) takes the torch route where the score matrix has strictly between these many entries: forward + backward
+# measured slower on the kernels at M = 2708, N' = 5416 (1.11x at d = 128, 1.69x at d = 256: too few workgroups), faster or level
+# at 1024 x 2048 = 2^21 and from 8192 x 16384 = 2^27 up; what lies between those two is unmeasured (profiles/contrast_bench.txt)
+_TORCH_FASTER = (1 << 21, 1 << 27)
+
+
+def slices(m, n, d, which):
+    """The slices csrc/contrast.hip cuts the walked side into: which = "fwd", "grad_q" or "grad_k"."""
+    return int(_lib.hip().cogdl_hip_pair_lse_slices(int(m), int(n), int(d), ("fwd", "grad_q", "grad_k").index(which)))
+
+
+def _hip_served(q):
+    return q.is_cuda and q.dtype == torch.float32 and q.shape[1] <= HIP_MAX_D
+
+
+class _HipLse(torch.autograd.Function):
+    """The kernels of csrc/contrast.hip.  Keeps q, k, skip, lse and corr ([M]: what lse * tau does not hold of a row's
+    normaliser in float32), and nothing else."""
+
+    @staticmethod
+    def forward(ctx, q, k, skip, tau, split):
+        (m, d), n = q.shape, k.shape[0]
+        dev = q.device
+        lse, corr = torch.empty(m, dtype=torch.float32, device=dev), torch.empty(m, dtype=torch.float32, device=dev)
+        n_slices = slices(m, n, d, "fwd") if split is None else split
+        ws, ws_bytes = _lib.workspace("cogdl_hip_pair_lse_workspace_bytes", dev, m, n, 2, n_slices)
+        with _lib.on_device(dev):
+            rc = _lib.hip().cogdl_hip_pair_lse_fwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(skip), m, n, d, tau, n_slices, _lib.ptr(lse),
+                                                   _lib.ptr(corr), _lib.ptr(ws), ws_bytes, _lib.stream_of(q))
+        _lib.check(rc, "pair_lse_fwd")
+        ctx.tau, ctx.split = tau, split
+        ctx.save_for_backward(q, k, skip, lse, corr)
+        ctx.mark_non_differentiable(corr)
+        return lse, corr
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad, _grad_corr):
+        q, k, skip, lse, corr = ctx.saved_tensors
+        (m, d), n = q.shape, k.shape[0]
+        dev = q.device
+        want_q, want_k = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_q or want_k):
+            return None, None, None, None, None
+        grad = grad.to(torch.float32).contiguous()
+        g_q = torch.empty_like(q) if want_q else None
+        g_k = torch.empty_like(k) if want_k else None
+        s_q = (slices(m, n, d, "grad_q") if ctx.split is None else ctx.split) if want_q else 1
+        s_k = (slices(m, n, d, "grad_k") if ctx.split is None else ctx.split) if want_k else 1
+        # one workspace, the larger of the two passes' (they run one after the other)
+        rows, other, n_slices = max([(m, n, s_q), (n, m, s_k)], key=lambda a: a[0] * a[2] * (a[2] > 1))
+        ws, ws_bytes = _lib.workspace("cogdl_hip_pair_lse_workspace_bytes", dev, rows, other, d, n_slices)
+        with _lib.on_device(dev):
+            rc = _lib.hip().cogdl_hip_pair_lse_grad(_lib.ptr(q), _lib.ptr(k), _lib.ptr(skip), _lib.ptr(lse), _lib.ptr(corr),
+                                                    _lib.ptr(grad), m, n, d, ctx.tau, s_q, s_k, _lib.ptr(g_q), _lib.ptr(g_k),
+                                                    _lib.ptr(ws), ws_bytes, _lib.stream_of(q))
+        _lib.check(rc, "pair_lse_grad")
+        return g_q, g_k, None, None, None
+
+
+def pair_lse(q, k, tau, skip=None, *, block=None, route=None, split=None, _skip_checked=False):
+    """q [M, d], k [N, d] -> lse [M] in the dtype of q.  route: None or "torch" -- the blocked composition (block: its query rows
+    per step), "hip" -- the kernels of csrc/contrast.hip (split: their slice count, for tests; by default the library's rule).
+    BackendError for arguments that are not 2-D floating tensors of one width and dtype, a tau that is not positive, a skip of
+    another shape, dtype or range, an unknown route, and for route="hip" on what the kernels do not serve: CPU tensors, a dtype
+    other than float32, d above 256."""
+    if route not in ROUTES:
+        raise _lib.BackendError("pair_lse: route must be one of %s (got %r)" % (ROUTES, route))
     if not (torch.is_tensor(q) and torch.is_tensor(k)) or q.dim() != 2 or k.dim() != 2 or q.shape[1] != k.shape[1]:
         raise _lib.BackendError("pair_lse: q and k must be 2-D of one width (got %s, %s)"
                                 % (tuple(getattr(q, "shape", ())), tuple(getattr(k, "shape", ()))))
@@ -135,17 +209,36 @@ def pair_lse(q, k, tau, skip=None, *, block=None, _skip_checked=False):
     tensors = [q, k] + ([] if skip is None else [skip])
     if len({t.device for t in tensors}) != 1:
         raise _lib.BackendError("pair_lse: tensors on %s" % sorted({str(t.device) for t in tensors}))
+    if route == "hip":
+        if not _hip_served(q):
+            raise _lib.BackendError("pair_lse: route=\"hip\" serves float32 CUDA tensors with d <= %d (got %s on %s, d = %d); "
+                                    "there is no fallback behind it" % (HIP_MAX_D, q.dtype, q.device, d))
+        if split is not None and int(split) < 1:
+            raise _lib.BackendError("pair_lse: split must be at least 1 (got %r)" % (split,))
+        if max(m, n) >= 2 ** 31 - 1:
+            raise _lib.BackendError("pair_lse: sizes beyond int32 indexing")
     if m == 0:
         return q.new_empty((0,))
+    if route == "hip":
+        skip32 = None if skip is None else skip.to(torch.int32).contiguous()
+        return _HipLse.apply(q.contiguous(), k.contiguous(), skip32, tau, None if split is None else int(split))[0]
     if q.is_cuda:
-        _note_torch_route("no HIP kernel serves this operator")
+        _note_torch_route("the blocked composition; route=\"hip\" runs the kernels of csrc/contrast.hip")
     return _BlockedLse.apply(q, k, skip, tau, _block_rows(q, k, block))
 
 
-def grace_loss(z1, z2, tau, *, block=None):
-    """The reference's GRACEModelWrapper.contrastive_loss(z1, z2) with self.tau = tau: z1 [M, d], z2 [N, d] -> scalar."""
+def grace_loss(z1, z2, tau, *, block=None, route=None):
+    """The reference's GRACEModelWrapper.contrastive_loss(z1, z2) with self.tau = tau: z1 [M, d], z2 [N, d] -> scalar.
+    route=None: the kernels for what they serve (float32 CUDA tensors, d <= 256) except where they measured slower
+    (_TORCH_FASTER: between 2^21 and 2^27 scores), the torch route for everything else; "torch" / "hip" as for pair_lse."""
+    if route not in ROUTES:
+        raise _lib.BackendError("grace_loss: route must be one of %s (got %r)" % (ROUTES, route))
     a = torch.nn.functional.normalize(z1, p=2, dim=-1)
     b = torch.nn.functional.normalize(z2, p=2, dim=-1)
+    if route is None:
+        served = a.dim() == 2 and b.dim() == 2 and a.shape[0] >= 1 and b.is_cuda and b.dtype == a.dtype and _hip_served(a)
+        scores = a.shape[0] * (a.shape[0] + b.shape[0]) if served else 0
+        route = "hip" if served and not _TORCH_FASTER[0] < scores < _TORCH_FASTER[1] else "torch"
     skip = torch.arange(a.shape[0], device=a.device)  # (in range by construction: M <= M + N keys)
-    lse = pair_lse(a, torch.cat([a, b]), tau, skip=skip, block=block, _skip_checked=True)
+    lse = pair_lse(a, torch.cat([a, b]), tau, skip=skip, block=block, route=route, _skip_checked=True)
     return torch.mean(lse - (a * a).sum(1) / float(tau))

@@ -1456,6 +1456,38 @@ COGDL_API int cogdl_hip_hin_score_grad(const float *Wx, const float *Wr, const i
                        const int32_t *chunk_ptr, int64_t B, int64_t N, int64_t R, int64_t D, int relation, float *grad,
                        float *partials, int64_t partial_rows, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Pairwise log-sum-exp (added within ABI v9: new symbols only; csrc/contrast.hip).  q fp32 [M, d], k fp32 [N, d], tau > 0,
+ * skip int32 [M] or NULL (an entry is only compared with key indices: one outside [0, N) skips nothing):
+ *     lse[i]    = log SUM_{j != skip[i]} exp(<q[i], k[j]> / tau)          fp32 [M]; an empty sum gives -inf
+ *     grad_q[i] = (g[i] / tau) SUM_j p_ij k[j]     grad_k[j] = (1 / tau) SUM_i g[i] p_ij q[i]     p_ij = exp(s_ij / tau - lse[i])
+ * with p_ij = 0 at j == skip[i] and in rows whose lse is -inf.  Nothing of size [M, N] exists: streaming fp32 MFMA tiles with an
+ * online {max, sum}; the backward recomputes the scores.  corr fp32 [M] is written by the forward and read by the backward
+ * together with lse (the part of the row's normaliser that lse tau does not hold in float32).  No float atomics, every sum
+ * in a fixed order: results are equal from run to run.
+ *   cogdl_hip_pair_lse_slices(M, N, d, which)  the slices of the walked side a pass is cut into (>= 1): which = 0 forward and
+ *       1 grad_q (workgroups own 64 queries and walk the keys), 2 grad_k (they own 64 keys and walk the queries).  Aims at 1024
+ *       workgroups; the slice partials stay within 64 MiB and within an eighth of M x N floats.
+ *   cogdl_hip_pair_lse_workspace_bytes(M, N, d, slices)  bytes of the partials of `slices` slices for an output of M rows and
+ *       d columns; 0 for one slice.  The forward's partials are (max, sum) pairs: ask with d = 2.  grad_k's output has N rows:
+ *       ask with (N, M, d, slices_k).
+ *   cogdl_hip_pair_lse_fwd    slices >= 1 (more than the walked side has tiles of 64: as many as it has).
+ *   cogdl_hip_pair_lse_grad   grad_q and / or grad_k may be NULL: that pass is not run.  Both passes use the one workspace, one
+ *       after the other: it holds the larger of the two requirements.  Every element of a wanted gradient is written.
+ * 1 <= d <= 256 (COGDL_HIP_EUNSUPPORTED above), N >= 1, M >= 0 (M == 0: lse is empty, grad_k is zeros); a tau that is not
+ * positive, a negative size or a NULL operand: COGDL_HIP_EINVAL; M or N of 2^31 - 1 and more: COGDL_HIP_ERANGE; pointers
+ * aligned to 4 bytes (COGDL_HIP_EALIGN otherwise; 16-byte loads are used where d % 4 == 0 and q and k are 16-byte aligned);
+ * a workspace that is too small: COGDL_HIP_EWORKSPACE.  Launches on `stream`; no allocation, no synchronisation, no host read.
+ * ------------------------------------------------------------------------------------------------------------------- */
+COGDL_API int64_t cogdl_hip_pair_lse_slices(int64_t M, int64_t N, int64_t d, int which);
+COGDL_API size_t cogdl_hip_pair_lse_workspace_bytes(int64_t M, int64_t N, int64_t d, int64_t slices);
+COGDL_API int cogdl_hip_pair_lse_fwd(const float *q, const float *k, const int32_t *skip, int64_t M, int64_t N, int64_t d,
+                       float tau, int64_t slices, float *lse, float *corr, void *workspace, size_t workspace_bytes,
+                       void *stream);
+COGDL_API int cogdl_hip_pair_lse_grad(const float *q, const float *k, const int32_t *skip, const float *lse, const float *corr,
+                       const float *g, int64_t M, int64_t N, int64_t d, float tau, int64_t slices_q, int64_t slices_k,
+                       float *grad_q, float *grad_k, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
