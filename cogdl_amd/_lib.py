@@ -74,6 +74,15 @@ HIP_SIGNATURES = {
     "cogdl_hip_rel_gspmm": ([_vp] * 7 + [_i32, _vp, _i64, _i64, _i64, _i64, _vp, _sz, _vp], _i32),
     "cogdl_hip_rel_gspmm_grad_rel_workspace_bytes": ([_i64, _i64], _sz),
     "cogdl_hip_rel_gspmm_grad_rel": ([_vp] * 7 + [_i32, _vp, _i64, _i64, _i64, _vp, _sz, _vp], _i32),
+    # RGCN message passing (csrc/rgcn.hip)
+    "cogdl_hip_rgcn_basis_workspace_bytes": ([_i64, _i64], _sz),
+    "cogdl_hip_rgcn_basis_fwd": ([_vp] * 8 + [_i64] * 5 + [_vp, _sz, _vp], _i32),
+    "cogdl_hip_rgcn_basis_grad_x": ([_vp] * 8 + [_i64] * 5 + [_vp, _sz, _vp], _i32),
+    "cogdl_hip_rgcn_basis_grad_alpha_workspace_bytes": ([_i64, _i64, _i64], _sz),
+    "cogdl_hip_rgcn_basis_grad_alpha": ([_vp] * 8 + [_i64] * 4 + [_vp, _sz, _vp], _i32),
+    "cogdl_hip_rgcn_bdd_fwd": ([_vp] * 8 + [_i64] * 6 + [_vp], _i32),
+    "cogdl_hip_rgcn_bdd_grad_w_workspace_bytes": ([_i64] * 5, _sz),
+    "cogdl_hip_rgcn_bdd_grad_w": ([_vp] * 8 + [_i64] * 5 + [_vp, _sz, _vp], _i32),
     # GENConv aggregation (csrc/genaggr.hip)
     "cogdl_hip_gen_aggr_fwd_workspace_bytes": ([_i64, _i64], _sz),
     "cogdl_hip_gen_aggr_fwd": ([_vp] * 5 + [_i32, _vp, _f32, _f32] + [_vp] * 3 + [_i64, _i64, _i64, _vp, _sz, _vp], _i32),

@@ -41,7 +41,7 @@ _finder = None
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
             metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False, readout=False,
             relational=False, genconv=False, disengcn=False, contrast=False, netsmf=False, metapath=False, prone=False,
-            kg_eval=False, kg_train=False, graph2vec=False, kg_sample=False, hin2vec=False, gatne=False, actnn=False, line=False):
+            kg_eval=False, kg_train=False, graph2vec=False, kg_sample=False, hin2vec=False, gatne=False, rgcn=False, actnn=False, line=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -95,8 +95,26 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     passing of the compgcn link-prediction model is one relational aggregation to [N, in] on the library's rel_gspmm operator
     (HIP kernels for CUDA tensors: no [E, in] / [E, out] message tensors, no float atomics, equal from run to run; the torch
     composition on the CPU) followed by one [N, in] x [in, out] matmul, instead of a matmul per edge and scatter_add_.  `opn`
-    "sub" and "mult" are served, any other reaches the reference's method.  The reference's RGCNLayer is not served
-    (INTEGRATION.md).
+    "sub" and "mult" are served, any other reaches the reference's method.  The reference's RGCNLayer is served by rgcn=True.
+    rgcn=True rebinds RGCNLayer.basis_forward and RGCNLayer.bdd_forward in cogdl.layers.rgcn_layer (opt-in: the layer computed is
+    the paper's law h[v] = sum_e n_e x[col_e] @ W[type_e], n_e = w_e / (sum of w over row v), not the reference's text) to
+    cogdl_amd.rgcn_compat: both return a one-element list, so RGCNLayer.forward -- sum, dropout, layer norm, bias, self loop --
+    runs unchanged.  Every deviation from the reference's text: (1) its basis_forward returns from inside the loop over the
+    edge types after the first type that has an edge (rgcn_layer.py:149), here every type contributes; (2) it aggregates over
+    the whole graph, `spmm(graph, h[edge_t])` (rgcn_layer.py:147), here a type's weight meets that type's edges only; (3) it
+    reads graph.edge_weight before graph.row_norm() (rgcn_layer.py:128-130), here the row-normalised weights of this call are
+    used; (4) its bdd_forward calls row_normalization(x.shape[0], edge_index, edge_weight) and spmm(_edge_index_t, weight,
+    h_t) (rgcn_layer.py:157,165), signatures neither function has, so it raises -- here n_e = 1 / (edges of row[e]); (5) the
+    sums are re-associated: basis is one aggregation to [N, B, in] (rgcn_basis_aggregate) and one [N, B * in] x [B * in, out]
+    matmul instead of [R, N, out] and one spmm per type, bdd (rgcn_bdd_aggregate) multiplies the sum of a (row, type) run by the
+    type's blocks instead of an einsum over all nodes and one spmm per type -- float32 rounding apart, the same numbers as the
+    law.  HIP kernels for CUDA tensors (csrc/rgcn.hip: nothing of size [E, .], nothing that scales with R * N, no float
+    atomics, equal from run to run), the torch composition on the CPU.  A graph without edge_attr reaches the reference's
+    method, which raises as before.  The constructor is NOT rebound, and the reference's raises for
+    regularizer="bdd" (reset_parameters reads self.alpha, which only the basis branch defines, rgcn_layer.py:95): the served
+    bdd_forward is reached only by a caller that builds the layer around that, e.g. registers the `alpha` buffer as None and
+    calls reset_parameters() again.  num_bases=None (one basis per type) is served by the kernels up to 32 types and by the
+    torch composition, with one TorchRouteWarning, beyond.
     genconv=True rebinds GENConv.forward in cogdl.layers.deepergcn_layer (opt-in: no longer the unchanged layer, and the softmax
     sums are re-associated -- float32 rounding apart, the same numbers) to cogdl_amd.genconv_compat: the aggregation of the
     deepergcn and revgcn models (gather, edge encoder term, relu + eps, beta, per-column edge softmax, multiply, scatter_add_)
@@ -390,6 +408,12 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
         _import_target(hin2vec_compat._MODULE, "hin2vec")
         if not hin2vec_compat.install():
             raise _lib_error("install(hin2vec=True): Hin2vec.forward could not be rebound")
+    if rgcn:
+        from . import rgcn_compat
+
+        _import_target(rgcn_compat._MODULE, "rgcn")
+        if not rgcn_compat.install():
+            raise _lib_error("install(rgcn=True): RGCNLayer.basis_forward / bdd_forward could not be rebound")
     su =sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):

@@ -16,6 +16,9 @@
 
     relational.py    rel_gspmm (also exported here)                    (CompGCNLayer.message_passing, models/nn/compgcn.py)
 
+    rgcn.py          rgcn_basis_aggregate, rgcn_bdd_aggregate (also exported here)   (RGCNLayer.basis_forward / bdd_forward,
+                                                                                      layers/rgcn_layer.py:118-168)
+
     genaggr.py       gen_aggregate (also exported here)                (GENConv.forward, layers/deepergcn_layer.py:67-93)
 
     disen.py         disen_route, neighbor_routing (also exported here)  (DisenGCNLayer.forward, layers/disengcn_layer.py:48-69)
@@ -79,6 +82,10 @@ def __getattr__(name):
         from . import relational
 
         return relational.rel_gspmm
+    if name in ("rgcn_basis_aggregate", "rgcn_bdd_aggregate"):
+        from . import rgcn
+
+        return getattr(rgcn, name)
     if name == "gen_aggregate":
         from . import genaggr
 

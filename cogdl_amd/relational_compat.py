@@ -8,9 +8,8 @@ aggregation to [N, in] (rel_gspmm: no [E, *] tensor, no atomics, equal from run 
 The sums are therefore re-associated against the reference's -- the same numbers up to float32 rounding, not the same bits.
 
 What does not: `opn` "sub" and "mult" are served; any other composition reaches the reference's own method
-(cogdl_amd/_rebind.original), which raises for it as before.  The reference's RGCNLayer is not served: its basis_forward
-returns from inside the loop over the edge types after the first one and aggregates over the whole graph
-(cogdl/layers/rgcn_layer.py:134-149), so there is no sound behaviour to reproduce.
+(cogdl_amd/_rebind.original), which raises for it as before.  The reference's RGCNLayer is served by `install(rgcn=True)`
+(cogdl_amd/rgcn_compat.py, INTEGRATION.md "RGCN").
 """
 import sys
 

@@ -484,6 +484,57 @@ COGDL_API int cogdl_hip_rel_gspmm_grad_rel(const int32_t *typeptr, const int32_t
                                  size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * RGCN message passing (csrc/rgcn.hip): every edge carries a type t and its message is the source row times a MATRIX W[t],
+ * h[v] = sum_{e: row[e] == v} w_e * x[col[e]] @ W[type[e]], in the two regularisations of the paper.  fp32, no float atomics,
+ * nothing of size [E, .] and nothing that scales with n_rel * N; every summation order is fixed by the sizes alone.
+ *
+ * basis, W[t] = sum_b alpha[t, b] V[b]: the sparse part is
+ *   z[v, b, :] = sum_{j in row v} weight[id_j] * alpha[etype[id_j], b] * x[colind[j], :],   id_j = eid ? eid[j] : j
+ * over the destination-sorted (CSR) view (z [m, n_bases, k]; the caller multiplies z.view(m, n_bases * k) by V), on the
+ * row-reduce engine: rows of up to cogdl_hip_exact_row_edges(nnz) edges are summed in edge order, longer rows in pieces merged
+ * in a fixed order.  alpha NULL = the identity (n_bases must equal n_rel).  n_bases <= 32 (COGDL_HIP_EUNSUPPORTED beyond), 8
+ * per pass over the edges.  etype as for cogdl_hip_rel_gspmm (clamped; the Python front refuses a bad id).
+ *   grad_x      over the SOURCE-sorted view (srcptr [n_src + 1], dst_sorted [E]):
+ *               grad_x[u, :] = sum_{j in row u} weight[id_j] * sum_b alpha[etype[id_j], b] * grad_z[dst_sorted[j], b, :]
+ *   grad_alpha  over the TYPE-sorted view (typeptr [n_rel + 1], src_sorted / dst_sorted [E], eid -> weight):
+ *               grad_alpha[t, b] = sum_{j in row t} weight[id_j] * <x[src_sorted[j], :], grad_z[dst_sorted[j], b, :]>
+ *               a type's edges in chunks of 64 dealt to S workgroups, S partials added in order.  nnz, k >= 1.
+ * ------------------------------------------------------------------------------------- */
+COGDL_API size_t cogdl_hip_rgcn_basis_workspace_bytes(int64_t nnz, int64_t k); /* forward and grad_x */
+COGDL_API int cogdl_hip_rgcn_basis_fwd(const int32_t *rowptr, const int32_t *colind, const int32_t *eid, const int32_t *etype,
+                             const float *x, const float *alpha, const float *weight, float *z, int64_t m, int64_t k,
+                             int64_t nnz, int64_t n_rel, int64_t n_bases, void *workspace, size_t workspace_bytes,
+                             void *stream);
+COGDL_API int cogdl_hip_rgcn_basis_grad_x(const int32_t *srcptr, const int32_t *dst_sorted, const int32_t *eid,
+                                const int32_t *etype, const float *grad_z, const float *alpha, const float *weight,
+                                float *grad_x, int64_t n_src, int64_t k, int64_t nnz, int64_t n_rel, int64_t n_bases,
+                                void *workspace, size_t workspace_bytes, void *stream);
+COGDL_API size_t cogdl_hip_rgcn_basis_grad_alpha_workspace_bytes(int64_t nnz, int64_t n_rel, int64_t n_bases);
+COGDL_API int cogdl_hip_rgcn_basis_grad_alpha(const int32_t *typeptr, const int32_t *src_sorted, const int32_t *dst_sorted,
+                                    const int32_t *eid, const float *x, const float *grad_z, const float *weight,
+                                    float *grad_alpha, int64_t n_rel, int64_t n_bases, int64_t k, int64_t nnz,
+                                    void *workspace, size_t workspace_bytes, void *stream);
+
+/* block diagonal, W[t] = diag of n_blocks blocks [bi, bo] (blocks [n_rel, n_blocks, bi, bo]; in = n_blocks * bi, out =
+ * n_blocks * bo), over a view sorted by (row, type) -- inside a row the edges of one type are adjacent:
+ *   out[v, b*bo:(b+1)*bo] = sum over the runs (v, t) of ( sum_{j in run} weight[id_j] * table[col_sorted[j], b*bi:(b+1)*bi] ) @ blocks[t, b]
+ *   col_sorted / type_sorted [E] gathered row and type of every edge in view order; eid view position -> edge id of weight.
+ *   Types are clamped into [0, n_rel) as in the basis entries (a bad id gives a wrong number, never a read outside blocks).
+ * One wave per row, one block multiply per run.  The gradient of x is the same entry over the (source, type)-sorted view with
+ * table = the upstream gradient and blocks transposed to [n_rel, n_blocks, bo, bi] (pass bi and bo swapped).
+ * in, out <= 512 and bi * bo <= 4096, COGDL_HIP_EUNSUPPORTED otherwise.
+ *   grad_w  over the TYPE-sorted view: grad_blocks[t, b, i, o] = sum_{j in row t} weight[id_j] * x[src_sorted[j], b*bi + i] *
+ *           grad[dst_sorted[j], b*bo + o]; a type's edges in chunks of 8 dealt to S workgroups, S partials added in order. */
+COGDL_API int cogdl_hip_rgcn_bdd_fwd(const int32_t *rowptr, const int32_t *col_sorted, const int32_t *type_sorted,
+                           const int32_t *eid, const float *table, const float *blocks, const float *weight, float *out,
+                           int64_t m, int64_t nnz, int64_t n_rel, int64_t n_blocks, int64_t bi, int64_t bo, void *stream);
+COGDL_API size_t cogdl_hip_rgcn_bdd_grad_w_workspace_bytes(int64_t nnz, int64_t n_rel, int64_t n_blocks, int64_t bi, int64_t bo);
+COGDL_API int cogdl_hip_rgcn_bdd_grad_w(const int32_t *typeptr, const int32_t *src_sorted, const int32_t *dst_sorted,
+                              const int32_t *eid, const float *x, const float *grad, const float *weight, float *grad_blocks,
+                              int64_t n_rel, int64_t n_blocks, int64_t bi, int64_t bo, int64_t nnz, void *workspace,
+                              size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * GENConv aggregation (csrc/genaggr.hip): the message passing of DeeperGCN's layer (cogdl/layers/deepergcn_layer.py:67-93:
  * gather x[col], add the encoded edge features, relu + eps, times beta, edge softmax with one channel per column, multiply,
  * scatter_add_) without any [E, k] tensor and without atomics.  Over the destination-sorted (CSR) view of the edges:
