@@ -41,7 +41,8 @@ _finder = None
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
             metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False, readout=False,
             relational=False, genconv=False, disengcn=False, contrast=False, netsmf=False, metapath=False, prone=False,
-            kg_eval=False, kg_train=False, graph2vec=False, kg_sample=False, hin2vec=False, gatne=False, rgcn=False, actnn=False, line=False):
+            kg_eval=False, kg_train=False, graph2vec=False, kg_sample=False, hin2vec=False, gatne=False, rgcn=False, recon=False, actnn=False,
+            line=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -115,6 +116,18 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     bdd_forward is reached only by a caller that builds the layer around that, e.g. registers the `alpha` buffer as None and
     calls reset_parameters() again.  num_bases=None (one basis per type) is served by the kernels up to 32 types and by the
     torch composition, with one TorchRouteWarning, beyond.
+    recon=True rebinds VGAE.make_loss in cogdl.models.nn.gae, DAEGC.recon_loss in cogdl.models.nn.daegc and
+    GAEModelWrapper.pre_stage in cogdl.wrappers.model_wrapper.clustering.gae_mw (opt-in: no longer the unchanged model, the sums are
+    re-associated, and the logs are not clamped at -100 as torch's binary_cross_entropy clamps them: a pair whose score exceeds
+    about 17 is charged its score, not 100) to cogdl_amd.recon_compat: binary_cross_entropy(sigmoid(z z^T), adj, reduction="sum")
+    against the dense [N, N] adjacency is one call of the library's inner_product_bce over the edges -- SUM softplus(<z_i, z_j>)
+    over all pairs minus SUM <z_row, z_col> over the edges (the MFMA kernels of csrc/recon.hip for float32 GPU tensors with
+    d <= 256: nothing of size [N, N] or [E, d], forward or backward, no float atomics, equal from run to run; a torch
+    composition in row blocks otherwise, on GPU tensors with one TorchRouteWarning).  VGAE.make_loss ignores its `adj`
+    argument and does not print the two terms; pre_stage leaves data.adj_mx = None for a VGAE and keeps the edges of stage 0
+    as data.recon_index, and is the reference's for any other model (GAE.make_loss has a row-softmax link and keeps its dense
+    adjacency); DAEGC.recon_loss takes a new optional `edge_index` and is the reference's whenever a dense adj is passed
+    (INTEGRATION.md).
     genconv=True rebinds GENConv.forward in cogdl.layers.deepergcn_layer (opt-in: no longer the unchanged layer, and the softmax
     sums are re-associated -- float32 rounding apart, the same numbers) to cogdl_amd.genconv_compat: the aggregation of the
     deepergcn and revgcn models (gather, edge encoder term, relu + eps, beta, per-column edge softmax, multiply, scatter_add_)
@@ -414,6 +427,13 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
         _import_target(rgcn_compat._MODULE, "rgcn")
         if not rgcn_compat.install():
             raise _lib_error("install(rgcn=True): RGCNLayer.basis_forward / bdd_forward could not be rebound")
+    if recon:
+        from . import recon_compat
+
+        for name in recon_compat.MODULES:
+            _import_target(name, "recon")
+        if not recon_compat.install():
+            raise _lib_error("install(recon=True): VGAE.make_loss / DAEGC.recon_loss / GAEModelWrapper.pre_stage could not be rebound")
     su =sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):

@@ -26,6 +26,9 @@
     contrast.py      pair_lse, grace_loss (also exported here)         (GRACEModelWrapper.contrastive_loss,
                                                                         wrappers/model_wrapper/node_classification/grace_mw.py:64-77)
 
+    recon.py         inner_product_bce (also exported here)            (VGAE.make_loss, models/nn/gae.py:76-84;
+                                                                        DAEGC.recon_loss, models/nn/daegc.py:82-84)
+
     netsmf.py        path_pairs, path_counts, sparsifier, randomized_svd (also exported here)   (models/emb/netsmf.py)
 
     spectral.py      filter_step, bessel_i, spectral_filter (also exported here)   (cogdl/utils/prone_utils.py:26-176,
@@ -98,6 +101,10 @@ def __getattr__(name):
         from . import contrast
 
         return getattr(contrast, name)
+    if name == "inner_product_bce":
+        from . import recon
+
+        return recon.inner_product_bce
     if name in ("path_pairs", "path_counts", "sparsifier", "randomized_svd"):
         from . import netsmf
 

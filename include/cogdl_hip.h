@@ -1539,6 +1539,38 @@ COGDL_API int cogdl_hip_pair_lse_grad(const float *q, const float *k, const int3
                        const float *g, int64_t M, int64_t N, int64_t d, float tau, int64_t slices_q, int64_t slices_k,
                        float *grad_q, float *grad_k, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Inner-product decoder loss (added within ABI v9: new symbols only; csrc/recon.hip).  z fp32 [N, d]; E weighted edges
+ * (row[e], col[e], w[e]), int32 endpoints in [0, N) -- the caller's to guarantee, they are not checked on the device --
+ * w fp32 [E] or NULL (all ones):
+ *     loss   = SUM_ij softplus(<z_i, z_j>) - SUM_e w[e] <z_row[e], z_col[e]>        over all ordered pairs, diagonal included
+ *     grad_z = 2 g sigmoid(Z Z^T) Z - g (A + A^T) Z                                 A = the dense sum of the weighted edges
+ * i.e. binary_cross_entropy(sigmoid(Z Z^T), A, reduction="sum") without the clamp of the logs at -100.  Nothing of size [N, N]
+ * or [E, d] exists: streaming fp32 MFMA tiles (the forward walks the tiles on and above the diagonal only), the backward
+ * recomputes the scores.  No float atomics, every sum in a fixed order: results are equal from run to run.
+ *   cogdl_hip_recon_bce_slices(N, d, which)  the slices the walked tiles of a row tile are cut into (>= 1): which = 0 forward,
+ *       1 backward.  Aims at 1024 workgroups; the backward's slice partials stay within 64 MiB and an eighth of N x N floats.
+ *   cogdl_hip_recon_bce_workspace_bytes(N, d, E, slices, which)  which = 0: one double per workgroup of the dense term and per run
+ *       of 256 edges; which = 1: `slices` [N, d] float blocks, 0 for one slice (E is not used).
+ *   cogdl_hip_recon_bce_fwd   row / col / w in any edge order; loss: one float in device memory.  slices >= 1 (more than there
+ *       are row tiles: as many as there are).  N == 0 (then E == 0) writes 0.
+ *   cogdl_hip_recon_bce_grad  g: one float in device memory (the upstream gradient).  rowptr int32 [N + 1], col int32 [E], w: the
+ *       edges sorted by row; tptr, tcol, tw: the same edges sorted by column, tcol holding the row.  rowptr and / or tptr NULL:
+ *       that gather is not run.  Every element of grad_z is written.
+ * 1 <= d <= 256 (COGDL_HIP_EUNSUPPORTED above); a negative size or a missing operand: COGDL_HIP_EINVAL; N or E of 2^31 - 1 and
+ * more: COGDL_HIP_ERANGE; pointers aligned to 4 bytes, the forward's workspace to 8 (COGDL_HIP_EALIGN otherwise; 16-byte loads
+ * are used where d % 4 == 0 and z is 16-byte aligned); a workspace that is too small: COGDL_HIP_EWORKSPACE.  Launches on
+ * `stream`; no allocation, no synchronisation, no host read.
+ * ------------------------------------------------------------------------------------------------------------------- */
+COGDL_API int64_t cogdl_hip_recon_bce_slices(int64_t N, int64_t d, int which);
+COGDL_API size_t cogdl_hip_recon_bce_workspace_bytes(int64_t N, int64_t d, int64_t E, int64_t slices, int which);
+COGDL_API int cogdl_hip_recon_bce_fwd(const float *z, const int32_t *row, const int32_t *col, const float *w, int64_t N,
+                       int64_t d, int64_t E, int64_t slices, float *loss, void *workspace, size_t workspace_bytes,
+                       void *stream);
+COGDL_API int cogdl_hip_recon_bce_grad(const float *z, const float *g, const int32_t *rowptr, const int32_t *col, const float *w,
+                       const int32_t *tptr, const int32_t *tcol, const float *tw, int64_t N, int64_t d, int64_t slices,
+                       float *grad_z, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
