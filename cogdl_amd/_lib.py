@@ -35,6 +35,11 @@ HIP_SIGNATURES = {
     "cogdl_hip_csr_spmm_xcd": ([_vp] * 4 + [_i64, _i64, _i32, _i32, _vp, _sz, _vp], _i32),
     "cogdl_hip_csr_spmm_sweep_group_rows": ([], _i32),
     "cogdl_hip_csr_spmm_sweep_round_rows": ([_i64, _i32], _i64),
+    "cogdl_hip_csr_spmm_sweep_xcds": ([], _i32),
+    "cogdl_hip_csr_spmm_sweep_block_waves": ([], _i32),
+    # the sweep's row-to-XCD partitioner (csrc/sweep_partition.hip)
+    "cogdl_hip_sweep_partition_workspace_bytes": ([_i64, _i64, _i32], _sz),
+    "cogdl_hip_sweep_partition": ([_vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _sz, _vp], _i32),
     "cogdl_hip_csr_spmm_sweep": ([_vp] * 5 + [_i64, _i64, _i64, _i32, _i64, _i64, _i32, _vp], _i32),
     "cogdl_hip_csr_spmm_sweep_guarded": ([_vp] * 5 + [_i64, _i64, _i64, _i32, _i64, _i64, _i32, _vp, _u64, _i32, _vp], _i32),
     "cogdl_hip_csr_spmm_sweep_rows": ([_vp] * 5 + [_i64, _i64, _i64, _i32, _i64, _i64, _i32, _vp, _i64, _vp], _i32),
@@ -295,6 +300,7 @@ HOST_SIGNATURES = {
     "cogdl_host_drop_apply": ([_vp, _i64, _u64, _u64, _u32, _f32, _vp], _i32),
     "cogdl_host_hin_pairs_count": ([_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp], _i32),
     "cogdl_host_hin_pairs_emit": ([_vp, _i64, _i64, _i32, _i64] + [_vp] * 4 + [_i64, _u64, _vp, _i64] + [_vp] * 5, _i32),
+    "cogdl_host_sweep_partition": ([_vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _sz], _i32),
 }
 
 EUNSUPPORTED = 7  # COGDL_HIP_EUNSUPPORTED

@@ -210,6 +210,9 @@ extern "C" int cogdl_hip_csr_spmm_xcd(const cogdl_hip_vrows *plan, const void *v
 
 // ---- sweep layout of a column-sorted structure (rowsweep.h) -----------------------------------------------------------------
 extern "C" int cogdl_hip_csr_spmm_sweep_group_rows(void) { return kSweepRows; }
+// (rowsweep.h: workgroups of 256 threads, wave0 = blockIdx.x * 4 + the wave's place in its workgroup)
+extern "C" int cogdl_hip_csr_spmm_sweep_xcds(void) { return kXcds; }
+extern "C" int cogdl_hip_csr_spmm_sweep_block_waves(void) { return 256 / kWave; }
 
 extern "C" int64_t cogdl_hip_csr_spmm_sweep_round_rows(int64_t k, int dtype) {
     if (dtype != COGDL_HIP_F32 || k != 2 * kWave) return 0;  // (rows of 512 bytes: one float2 per lane)

@@ -23,6 +23,7 @@ returns one): the same layout with the local row being the row's slot in its gro
   rows [n_groups * r]  the row map the kernel stores through (csrc/rowsweep.h: MAPPED)
 The layouts the policy builds (`of`, `register_forward`) take `deal_by_degree`: consecutive rows give waves whose edge counts
 differ by +-4 %, and a wave with 4 % fewer edges is 4 % of the table ahead at the same edge index -- more than an XCD's L2 holds.
+They take it through `deal_by_xcd`, which first decides which XCD a row runs on: rows that gather the same rows share an L2.
 Built with torch ops on whatever device the structure's tensors live on (the tests build it on the CPU).  The backward's layout is
 built lazily and kept on the transpose's plan; the forward's lives in a cache of its own (`FORWARD`, keyed by the structure's
 Fingerprint key, outside the plan cache's byte count).
@@ -37,6 +38,7 @@ from . import plan as _plan
 
 LOCAL_SHIFT = 24            # tables of < 2^24 rows (as the XCD plans assume); local rows < 2^7
 MAX_TABLE_ROWS = 1 << 23    # ... and 512-byte rows at 32-bit byte offsets (csrc/rowsweep.h)
+SWEEP_WIDTH = 128           # the one width (fp32 columns) the sweep kernels take
 
 
 class SweepPlan:
@@ -102,8 +104,8 @@ def _grouped(ptr, row, key, col, n_rows, n_src, r, assign):
         goff = ptr[torch.clamp(torch.arange(n_groups + 1, device=dev) * r, max=n_rows)].int()
         rows = None
     else:
-        if callable(assign):  # (a procedure that wants the merge key: deal_by_degree)
-            assign = assign(ptr, r, key)
+        if callable(assign):  # (a procedure that wants the merge key: deal_by_degree; and the gathered rows: deal_by_xcd)
+            assign = assign(ptr, r, key, col, n_src) if getattr(assign, "takes_col", False) else assign(ptr, r, key)
         flat = checked_assignment(assign.to(dev), n_rows, r)
         n_groups = flat.numel() // r
         slot = torch.empty(n_rows, dtype=torch.long, device=dev)
@@ -161,6 +163,17 @@ def build_forward(rowptr, colind, n_src, r, assign=None):
     return SweepPlan(goff, src, order.int().contiguous(), r, m, n_src, out_of_order, long_rows, rows=rows)
 
 
+def _rows_by_degree(p, key):
+    """The order rows are dealt in: by edge count (descending, stable); with `key`, equal counts by ascending mean key."""
+    deg = p[1:] - p[:-1]
+    if key is None or key.numel() == 0:
+        return torch.sort(deg, descending=True, stable=True).indices
+    total = torch.cat([p.new_zeros(1), torch.cumsum(key.long(), 0)])
+    mean = (total[p[1:]] - total[p[:-1]]).double() / deg.clamp(min=1).double()
+    by_mean = torch.sort(mean, stable=True).indices
+    return by_mean[torch.sort(deg[by_mean], descending=True, stable=True).indices]
+
+
 def deal_by_degree(ptr, r, key=None):
     """-> an assignment [n_groups, r] (int64; -1 = pad) of the rows of `ptr` ([n_rows + 1]) to n_groups = ceil(n_rows / r)
     groups: rows sorted by edge count (descending, stable) and dealt over the groups boustrophedon -- round 0 left to right,
@@ -175,15 +188,7 @@ def deal_by_degree(ptr, r, key=None):
     r = int(r)
     n_rows = ptr.numel() - 1
     n_groups = (n_rows + r - 1) // r
-    p = ptr.long()
-    deg = p[1:] - p[:-1]
-    if key is None or key.numel() == 0:
-        by_degree = torch.sort(deg, descending=True, stable=True).indices
-    else:
-        total = torch.cat([p.new_zeros(1), torch.cumsum(key.long(), 0)])
-        mean = (total[p[1:]] - total[p[:-1]]).double() / deg.clamp(min=1).double()
-        by_mean = torch.sort(mean, stable=True).indices
-        by_degree = by_mean[torch.sort(deg[by_mean], descending=True, stable=True).indices]
+    by_degree = _rows_by_degree(ptr.long(), key)
     at = torch.arange(n_rows, device=ptr.device)
     rnd = torch.div(at, max(n_groups, 1), rounding_mode="floor")
     j = at - rnd * n_groups
@@ -193,9 +198,102 @@ def deal_by_degree(ptr, r, key=None):
     return assign.view(n_groups, r)
 
 
+def group_xcd(n_groups, device=None):
+    """-> (xcd [n_groups] of every group, n_xcd): group g is wave g of the grid, the library's waves per workgroup make a
+    workgroup, and workgroup b runs on XCD b % n_xcd (include/cogdl_hip.h: cogdl_hip_csr_spmm_sweep_xcds)."""
+    lib = _lib.hip()
+    n_xcd, block_waves = int(lib.cogdl_hip_csr_spmm_sweep_xcds()), int(lib.cogdl_hip_csr_spmm_sweep_block_waves())
+    g = torch.arange(n_groups, device=device)
+    return torch.div(g, block_waves, rounding_mode="floor") % n_xcd, n_xcd
+
+
+def _rounds_keep_xcds(n_groups, n_xcd, dev):
+    """group_xcd's rule holds for the groups of later rounds too (group g is wave g % the round's waves) only if a round's
+    waves are a multiple of waves per workgroup * n_xcd: true on a whole device, asked here in case it is not (a device
+    partition, tuning key 18).  One round, or no device to ask (CPU tensors: layouts for the tests): yes."""
+    if dev.type != "cuda":
+        return True
+    lib = _lib.hip()
+    with _lib.on_device(dev):
+        waves = int(lib.cogdl_hip_csr_spmm_sweep_round_rows(SWEEP_WIDTH, _lib.DTYPE_CODE[torch.float32])) // int(lib.cogdl_hip_csr_spmm_sweep_group_rows())
+    return n_groups <= waves or waves % (int(lib.cogdl_hip_csr_spmm_sweep_block_waves()) * n_xcd) == 0
+
+
+def partition_rows(ptr, ind, n_src, n_parts, capacity, rounds, labels):
+    """-> labels [n_rows] (int32) after `rounds` rounds of the partitioner (csrc/sweep_partition_law.h) from the starting
+    `labels`: the kernels for CUDA tensors, their host twin otherwise -- equal labels either way.  capacity [n_parts]: the rows
+    a part may hold; rows only swap parts, so it is the starting labels that are held to it."""
+    dev = ptr.device
+    n_rows = ptr.numel() - 1
+    ptr32, ind32 = ptr.int().contiguous(), ind.int().contiguous()
+    out = labels.int().contiguous().clone()
+    if n_rows and (int(out.min()) < 0 or int(out.max()) >= n_parts):
+        raise _lib.BackendError("sweep partition: a starting label outside the %d parts" % n_parts)
+    if bool((torch.bincount(out.long(), minlength=n_parts) > capacity.to(dev)).any()):
+        raise _lib.BackendError("sweep partition: the starting labels exceed a part's capacity")
+    ws, ws_bytes = (_lib.workspace("cogdl_hip_sweep_partition_workspace_bytes", dev, n_rows, n_src, n_parts)
+                    if dev.type == "cuda" else (None, 0))
+    _lib.twin_call("sweep_partition", dev, _lib.ptr(ptr32), _lib.ptr(ind32), n_rows, ind32.numel(), int(n_src), int(n_parts),
+                   int(rounds), _lib.ptr(out), _lib.ptr(ws), ws_bytes)
+    return out
+
+
+# Rounds of the partitioner in deal_by_xcd: the shared gathered rows it finds per round against the build time a round adds
+# (profiles/sweep_xcd.txt, sections 1 and 4).
+XCD_ROUNDS = 8
+
+
+def deal_by_xcd(ptr, r, key, col, n_src, rounds=None):
+    """-> an assignment [n_groups, r] like deal_by_degree's, of the same n_groups = ceil(n_rows / r) groups, made in two steps.
+    Which XCD: every row starts on the XCD a degree deal gives it, then the partitioner (partition_rows) lets rows of equal
+    edge count swap XCDs so that rows gathering the same rows of the table (`col`, [nnz]) meet on one XCD -- a shared gathered
+    row is then one miss of that XCD's L2, not one per XCD.  Rows and edges per XCD stay what the deal made them.
+    Which group: inside an XCD, deal_by_degree's deal over that XCD's groups (by edge count, equal counts by mean key,
+    boustrophedon, pads last): max - min edges per group of an XCD <= its largest row.
+    Every row keeps its own edge order in whatever group it sits, so the sums stay bit-identical.
+    deal_by_degree itself where there is nothing to gain: one XCD, fewer than 4 groups per XCD, no edges."""
+    r = int(r)
+    n_rows = ptr.numel() - 1
+    n_groups = (n_rows + r - 1) // r
+    dev = ptr.device
+    xcd, n_xcd = group_xcd(n_groups, dev)
+    if n_xcd == 1 or n_groups < 4 * n_xcd or col.numel() == 0 or not _rounds_keep_xcds(n_groups, n_xcd, dev):
+        return deal_by_degree(ptr, r, key)
+    groups_of = torch.bincount(xcd, minlength=n_xcd)
+    first_of = torch.cumsum(groups_of, 0) - groups_of
+    by_xcd = torch.sort(xcd, stable=True).indices  # the groups XCD by XCD
+    # Where a row starts: the deal itself, over the groups taken in turn across the XCDs (every XCD's first group, every
+    # XCD's second, ...).  Over the groups as numbered, a deal hands XCD 0 the longer row of every workgroup-sized run, all
+    # the way down the sorted rows; taken in turn, the XCDs' differences telescope like the groups' do.
+    nth = torch.arange(n_groups, device=dev) - first_of[xcd[by_xcd]]
+    in_turn = by_xcd[torch.sort(nth * n_xcd + xcd[by_xcd], stable=True).indices]
+    order = _rows_by_degree(ptr.long(), key)
+    at = torch.arange(n_rows, device=dev)
+    rnd = torch.div(at, n_groups, rounding_mode="floor")
+    j = at - rnd * n_groups
+    start = torch.empty(n_rows, dtype=torch.long, device=dev)
+    start[order] = xcd[in_turn[torch.where(rnd % 2 == 0, j, n_groups - 1 - j)]]
+    labels = partition_rows(ptr, col, n_src, n_xcd, groups_of * r, XCD_ROUNDS if rounds is None else rounds, start).long()
+    # the rows in dealing order, XCD by XCD
+    order = order[torch.sort(labels[order], stable=True).indices]
+    part = labels[order]
+    rows_of = torch.bincount(labels, minlength=n_xcd)
+    at = torch.arange(n_rows, device=dev) - (torch.cumsum(rows_of, 0) - rows_of)[part]
+    width = groups_of[part]
+    rnd = torch.div(at, width, rounding_mode="floor")
+    j = at - rnd * width
+    j = torch.where(rnd % 2 == 0, j, width - 1 - j)
+    group = by_xcd[first_of[part] + j]
+    assign = torch.full((n_groups * r,), -1, dtype=torch.long, device=dev)
+    assign[group * r + rnd] = order
+    return assign.view(n_groups, r)
+
+
+deal_by_xcd.takes_col = True  # (_grouped hands such a procedure the gathered rows and the table's size as well)
+
 # Which rows share a group in the layouts the policy builds (`of`, `register_forward`): a tensor-returning procedure
-# (ptr, r, key), or None for r consecutive rows.
-ASSIGN = deal_by_degree
+# (ptr, r, key) -- with `takes_col`, (ptr, r, key, col, n_src) -- or None for r consecutive rows.
+ASSIGN = deal_by_xcd
 
 
 class ForwardCache:

@@ -177,6 +177,29 @@ COGDL_API int cogdl_hip_csr_spmm_xcd(const cogdl_hip_vrows *plan, const void *va
  * Tuning key 18 caps the rows of one round (tests). */
 COGDL_API int cogdl_hip_csr_spmm_sweep_group_rows(void);
 COGDL_API int64_t cogdl_hip_csr_spmm_sweep_round_rows(int64_t k, int dtype);
+/* Where a group runs: group g is walked by wave g of the grid (a further round by the same waves), cogdl_hip_csr_spmm_sweep_block_waves()
+ * waves make a workgroup, and workgroup b runs on XCD b % cogdl_hip_csr_spmm_sweep_xcds() -- as long as one round's waves are a
+ * multiple of their product, which they are on a whole device. */
+COGDL_API int cogdl_hip_csr_spmm_sweep_xcds(void);
+COGDL_API int cogdl_hip_csr_spmm_sweep_block_waves(void);
+
+/* Which XCD the rows of a sweep layout should run on (csrc/sweep_partition_law.h is the law, word for word): rows that share
+ * gathered rows are brought onto the same XCD, where the shared row is one L2 miss instead of several.
+ *   ptr [n_rows + 1], ind [nnz]   the structure: the gathered row (< n_src) of every edge, rows in any inner order
+ *   labels [n_rows]               in: the part in [0, n_parts) every row starts in; out: the part it ends in
+ * `rounds` rounds of: count, per (gathered row, part), the edges of the part that gather it; score every row against every
+ * part without its own edges; rows whose best part is another one swap with rows of the SAME edge count that want to go the
+ * other way, highest gain first, equal gains by ascending row, half of each matched set per round (a set of more than 2048
+ * candidates waits: nobody of it moves in that round, which bounds a round's cost on regular graphs).  Rows per part and edges
+ * per part are therefore exactly those of the starting labels.  Integer arithmetic; atomics only build counts; the same input
+ * gives the same labels on every launch and in cogdl_host_sweep_partition.  n_parts <= 8; rows of 64 edges or more, rows
+ * without edges, and rows whose label is out of range stay; an edge whose gathered row is out of range counts nowhere.
+ * Stream-ordered, no synchronisation.  workspace: cogdl_hip_sweep_partition_workspace_bytes(n_rows, n_src, n_parts) bytes,
+ * 8-byte aligned. */
+COGDL_API size_t cogdl_hip_sweep_partition_workspace_bytes(int64_t n_rows, int64_t n_src, int n_parts);
+COGDL_API int cogdl_hip_sweep_partition(const int32_t *ptr, const int32_t *ind, int64_t n_rows, int64_t nnz, int64_t n_src,
+                                        int n_parts, int rounds, int32_t *labels, void *workspace, size_t workspace_bytes,
+                                        void *stream);
 COGDL_API int cogdl_hip_csr_spmm_sweep(const int32_t *goff, const int32_t *src, const void *w, const void *x, void *out,
                                        int64_t m, int64_t n_src, int64_t n_groups, int r, int64_t k, int64_t nnz, int dtype,
                                        void *stream);

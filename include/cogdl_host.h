@@ -275,6 +275,13 @@ COGDL_HOST_API int cogdl_host_hin_pairs_emit(const int64_t *walks, int64_t W, in
                                              const int32_t *rank, int64_t N, uint64_t seed, const int64_t *offsets,
                                              int64_t total, int64_t *x, int64_t *y, int64_t *key, int64_t *label, int *flags);
 
+/* The sweep's row-to-XCD partitioner; the host twin of cogdl_hip_sweep_partition (include/cogdl_hip.h, where the contract is
+ * spelled out): same arguments minus the stream, all pointers host memory, `workspace` is not read.  Both sides follow
+ * csrc/sweep_partition_law.h, so for equal inputs the labels are the GPU's.  Checked here, since it is cheap on the host:
+ * a label outside [0, n_parts) or a gathered row outside [0, n_src) is COGDL_HOST_ERANGE. */
+COGDL_HOST_API int cogdl_host_sweep_partition(const int32_t *ptr, const int32_t *ind, int64_t n_rows, int64_t nnz, int64_t n_src,
+                                              int n_parts, int rounds, int32_t *labels, void *workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

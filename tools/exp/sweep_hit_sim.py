@@ -93,6 +93,18 @@ def layout(ptr, ind, assign, forward=False):
     return goff, ind[order]
 
 
+def xcd_pairs(ptr, ind, assign, xcds=8, waves_per_workgroup=4):
+    """-> the distinct (XCD, gathered row) pairs of an assignment walked in one round: what `simulate` calls ideal, as a count."""
+    ptr, ind = np.asarray(ptr, dtype=np.int64), np.asarray(ind, dtype=np.int64)
+    n_groups, r = assign.shape
+    flat = assign.reshape(-1)
+    real = np.nonzero(flat >= 0)[0]
+    xcd_of = np.empty(len(ptr) - 1, dtype=np.int64)
+    xcd_of[flat[real]] = (real // r // waves_per_workgroup) % xcds
+    row = np.repeat(np.arange(len(ptr) - 1), np.diff(ptr))
+    return len(np.unique(xcd_of[row] * (int(ind.max()) + 1 if len(ind) else 1) + ind))
+
+
 def simulate(goff, gathered, n_waves=4096, capacities=CAPACITIES, xcds=8, waves_per_workgroup=4):
     """-> {"gathers", "ideal", capacity: hit rate, ...} of the lockstep model above."""
     n_groups = len(goff) - 1
