@@ -245,6 +245,10 @@ HIP_SIGNATURES = {
     "cogdl_hip_recon_bce_workspace_bytes": ([_i64, _i64, _i64, _i64, _i32], _sz),
     "cogdl_hip_recon_bce_fwd": ([_vp] * 4 + [_i64] * 4 + [_vp, _vp, _sz, _vp], _i32),
     "cogdl_hip_recon_bce_grad": ([_vp] * 8 + [_i64] * 3 + [_vp, _vp, _sz, _vp], _i32),
+    # ragged segment GEMMs (csrc/segmm.hip)
+    "cogdl_hip_segment_matmul_workspace_bytes": ([_i64] * 7, _sz),
+    "cogdl_hip_segment_matmul_tn": ([_vp] * 5 + [_i64] * 7 + [_vp] * 4 + [_sz, _vp], _i32),
+    "cogdl_hip_segment_matmul_nn": ([_vp] * 3 + [_i64] * 4 + [_i32, _vp, _vp], _i32),
 }
 
 MAX_SEGMENTS = 64  # COGDL_HIP_MAX_SEGMENTS

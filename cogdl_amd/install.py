@@ -41,8 +41,8 @@ _finder = None
 def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, fused_gat_dropout=False, structure_memo=False,
             metis=False, big_graphs=False, torch_sparse=False, random_walk=False, ppr=False, skipgram=False, readout=False,
             relational=False, genconv=False, disengcn=False, contrast=False, netsmf=False, metapath=False, prone=False,
-            kg_eval=False, kg_train=False, graph2vec=False, kg_sample=False, hin2vec=False, gatne=False, rgcn=False, recon=False, actnn=False,
-            line=False):
+            kg_eval=False, kg_train=False, graph2vec=False, kg_sample=False, hin2vec=False, gatne=False, rgcn=False, recon=False,
+            diffpool=False, actnn=False, line=False):
     """Idempotent.  Returns the list of cogdl module names that are now served by cogdl_amd.
     fused_norm=True rebinds the dispatcher function `cogdl.utils.spmm_utils.spmm` itself (opt-in: that is no longer the
     unchanged dispatcher) to cogdl_amd.fused.spmm, which folds `out_norm * x` / `in_norm * x` into the kernel.
@@ -128,6 +128,17 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     as data.recon_index, and is the reference's for any other model (GAE.make_loss has a row-softmax link and keeps its dense
     adjacency); DAEGC.recon_loss takes a new optional `edge_index` and is the reference's whenever a dense adj is passed
     (INTEGRATION.md).
+    diffpool=True rebinds BatchedDiffPoolLayer.forward in cogdl.models.nn.diffpool (opt-in: no longer the unchanged layer; the
+    assignment is the exact softmax of each node's own K columns where the reference divides by the row sum + 1e-13; the sums
+    are re-associated, the link loss from three float64 scalars; N is x.shape[0], not the largest node id in an edge) to
+    cogdl_amd.diffpool_compat: the pooling of the diffpool model is one csrspmm (A S) and one three-panel launch of the
+    library's segment_matmul_tn -- S_g^T embed_g, S_g^T (A S)_g and S_g^T S_g for every graph g of the batch (the MFMA kernels of
+    csrc/segmm.hip for float32 GPU tensors, whose gradient is segment_matmul_nn; the padded torch composition on the CPU) --
+    instead of a [N, B * K] block mask built on the CPU with scipy, [B * K, N] products that are zero outside one block per
+    graph, and adj.to_dense() with result @ result.t() as [N, N] for the link loss.  adj_new keeps its [B * K, B * K] shape with
+    the blocks on the diagonal; the loss_dict keys and the return order are unchanged.  A `pooled` width the number of graphs
+    does not divide, an unsorted batch, an edge_weight that requires grad, an x that is not 2-D float32, a graph whose CSR does
+    not describe its edge_index and an edge between two graphs of the batch reach the reference's forward.
     genconv=True rebinds GENConv.forward in cogdl.layers.deepergcn_layer (opt-in: no longer the unchanged layer, and the softmax
     sums are re-associated -- float32 rounding apart, the same numbers) to cogdl_amd.genconv_compat: the aggregation of the
     deepergcn and revgcn models (gather, edge encoder term, relu + eps, beta, per-column edge softmax, multiply, scatter_add_)
@@ -434,6 +445,12 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
             _import_target(name, "recon")
         if not recon_compat.install():
             raise _lib_error("install(recon=True): VGAE.make_loss / DAEGC.recon_loss / GAEModelWrapper.pre_stage could not be rebound")
+    if diffpool:
+        from . import diffpool_compat
+
+        _import_target(diffpool_compat._MODULE, "diffpool")
+        if not diffpool_compat.install():
+            raise _lib_error("install(diffpool=True): BatchedDiffPoolLayer.forward could not be rebound")
     su =sys.modules.get("cogdl.utils.spmm_utils")
     if su is not None:  # force the dispatcher to re-resolve the callables
         for k in ("spmm_flag", "mh_spmm_flag", "fused_gat_flag", "spmm_cpu_flag"):

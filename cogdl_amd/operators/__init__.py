@@ -29,6 +29,9 @@
     recon.py         inner_product_bce (also exported here)            (VGAE.make_loss, models/nn/gae.py:76-84;
                                                                         DAEGC.recon_loss, models/nn/daegc.py:82-84)
 
+    segmm.py         segment_matmul_tn, segment_matmul_nn, diffpool_coarsen (also exported here)
+                                                                       (BatchedDiffPoolLayer.forward, models/nn/diffpool.py:152-180)
+
     netsmf.py        path_pairs, path_counts, sparsifier, randomized_svd (also exported here)   (models/emb/netsmf.py)
 
     spectral.py      filter_step, bessel_i, spectral_filter (also exported here)   (cogdl/utils/prone_utils.py:26-176,
@@ -105,6 +108,10 @@ def __getattr__(name):
         from . import recon
 
         return recon.inner_product_bce
+    if name in ("segment_matmul_tn", "segment_matmul_nn", "diffpool_coarsen"):
+        from . import segmm
+
+        return getattr(segmm, name)
     if name in ("path_pairs", "path_counts", "sparsifier", "randomized_svd"):
         from . import netsmf
 

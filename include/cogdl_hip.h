@@ -1594,6 +1594,35 @@ COGDL_API int cogdl_hip_recon_bce_grad(const float *z, const float *g, const int
                        const int32_t *tptr, const int32_t *tcol, const float *tw, int64_t N, int64_t d, int64_t slices,
                        float *grad_z, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Ragged segment GEMMs (added within ABI v9: new symbols only; csrc/segmm.hip).  fp32.  ptr int64 [B + 1] in DEVICE memory,
+ * non-decreasing with ptr[0] = 0 and ptr[B] = N -- the caller's to guarantee: it is never read on the host, and a malformed
+ * one gives wrong numbers, never an access outside the operands.  g(i): the segment with ptr[g] <= i < ptr[g + 1].
+ *     tn   out_p[g] = S[ptr[g] : ptr[g + 1]]^T X_p[ptr[g] : ptr[g + 1]]     S [N, K], X_p [N, F_p], out_p [B, K, F_p]
+ *     nn   out[i] (+)= X[i] W[g(i)]                                          X [N, P], W [B, P, Q], out [N, Q]
+ * Each is the other's gradient.  v_mfma_f32_32x32x2_f32 tiles; no float atomics, every sum in a fixed order: equal bytes from
+ * run to run.
+ *   cogdl_hip_segment_matmul_tn  one to three right-hand panels x0, x1, x2 of widths F0 >= 1, F1, F2 (a width of 0: the panel
+ *       and every later one is absent, its pointers are not read), each with its own output; a panel may be s itself.  The left
+ *       operand is staged once per group of four 64-column tiles of the panels.  split >= 1: every segment's rows are cut into
+ *       that many proportional slices (at most 1024) whose partial tiles go to the workspace and are added in slice order;
+ *       split = 0: a number chosen from N, B and the tile counts.  Every element of every output is written (an empty segment:
+ *       zeros).  B == 0: nothing is written.
+ *   cogdl_hip_segment_matmul_workspace_bytes  for the same sizes and the same `split`: 0 where one slice is used.
+ *   cogdl_hip_segment_matmul_nn  accumulate != 0: adds to `out` (the terms of a gradient summed in one buffer), else every
+ *       element of out is written, a row no segment holds as zeros.
+ * Sizes that are negative, K, F0, P or Q < 1: COGDL_HIP_EINVAL; a size or a launch grid of 2^31 - 1 and more, split > 1024:
+ * COGDL_HIP_ERANGE; pointers aligned to 4 bytes, ptr to 8 (COGDL_HIP_EALIGN otherwise; only 4-byte loads are issued); a
+ * workspace that is too small: COGDL_HIP_EWORKSPACE.  Launches on `stream`; no allocation, no synchronisation, no host read.
+ * ------------------------------------------------------------------------------------------------------------------- */
+COGDL_API size_t cogdl_hip_segment_matmul_workspace_bytes(int64_t N, int64_t B, int64_t K, int64_t F0, int64_t F1, int64_t F2,
+                       int64_t split);
+COGDL_API int cogdl_hip_segment_matmul_tn(const float *s, const float *x0, const float *x1, const float *x2, const int64_t *ptr,
+                       int64_t N, int64_t B, int64_t K, int64_t F0, int64_t F1, int64_t F2, int64_t split, float *out0,
+                       float *out1, float *out2, void *workspace, size_t workspace_bytes, void *stream);
+COGDL_API int cogdl_hip_segment_matmul_nn(const float *x, const float *w, const int64_t *ptr, int64_t N, int64_t B, int64_t P,
+                       int64_t Q, int accumulate, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
