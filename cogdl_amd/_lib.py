@@ -240,6 +240,9 @@ HIP_SIGNATURES = {
     "cogdl_hip_pair_lse_workspace_bytes": ([_i64, _i64, _i64, _i64], _sz),
     "cogdl_hip_pair_lse_fwd": ([_vp, _vp, _vp, _i64, _i64, _i64, _f32, _i64, _vp, _vp, _vp, _sz, _vp], _i32),
     "cogdl_hip_pair_lse_grad": ([_vp] * 6 + [_i64, _i64, _i64, _f32, _i64, _i64, _vp, _vp, _vp, _sz, _vp], _i32),
+    "cogdl_hip_pair_lse16_workspace_bytes": ([_i64, _i64, _i64, _i64], _sz),
+    "cogdl_hip_pair_lse16_fwd": ([_vp, _vp, _i32, _vp, _i64, _i64, _i64, _f32, _i64, _vp, _vp, _vp, _sz, _vp], _i32),
+    "cogdl_hip_pair_lse16_grad": ([_vp, _vp, _i32] + [_vp] * 4 + [_i64, _i64, _i64, _f32, _i64, _i64, _vp, _vp, _vp, _sz, _vp], _i32),
     # inner-product decoder loss (csrc/recon.hip)
     "cogdl_hip_recon_bce_slices": ([_i64, _i64, _i32], _i64),
     "cogdl_hip_recon_bce_workspace_bytes": ([_i64, _i64, _i64, _i64, _i32], _sz),

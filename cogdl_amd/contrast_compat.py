@@ -9,7 +9,9 @@ subtracted from it, and the sums go through logsumexp, so they are re-associated
 float32 rounding, not the same bits -- and finite where the reference's plain exp overflows (tau below about 0.0113).  On
 float32 GPU tensors with d <= 256 grace_loss runs the streaming MFMA kernels of csrc/contrast.hip, except at the sizes where
 they measured slower than the blocked torch composition (profiles/contrast_bench.txt); everything else runs that composition,
-on the GPU with one TorchRouteWarning.
+on the GPU with one TorchRouteWarning.  Under torch.autocast for the GPU, float32 and 16-bit inputs with d <= 256 are normalised in
+float32, cast once to the autocast dtype and run on the fp16 / bf16 kernels of csrc/contrast16.hip (v_mfma_f32_32x32x16) at the
+sizes where those measured no slower; the loss is float32 and the gradients come back in the inputs' own dtype.
 
 What does not: `batched_loss` (lines 79-91) calls `self.contrastive_loss(z1[idx], z2)` and is served as it stands; `train_step`
 and everything else are the reference's.  Inputs that are not 2-D floating tensors of one width, dtype and device reach the
@@ -34,6 +36,11 @@ def _served(z1, z2):
 def contrastive_loss(self, z1, z2):
     if not _served(z1, z2):
         return _rebind.original(getattr(sys.modules[_MODULE], _CLASS), "contrastive_loss")(self, z1, z2)
+    if z1.is_cuda and torch.is_autocast_enabled() and torch.get_autocast_gpu_dtype() in (torch.float16, torch.bfloat16):
+        # torch AMP (the Trainer's fp16=True): whatever dtype the projection head handed over, the rows are normalised in float32,
+        # cast once to the autocast dtype for this one call and run on the 16-bit kernels; the loss is float32 and the gradient
+        # reaches z1, z2 in their own dtype through the cast.  Outside autocast nothing is cast.
+        return grace_loss(z1, z2, self.tau, cast=torch.get_autocast_gpu_dtype())
     return grace_loss(z1, z2, self.tau)
 
 

@@ -160,7 +160,10 @@ def install(linear=False, fused_gat=True, fused_norm=False, narrow_side=False, f
     cogdl_amd.contrast_compat: the loss of the grace model is one call of the library's grace_loss (normalisation, then the
     pair_lse operator, whose backward recomputes the scores, so neither of the two [N, N] score matrices is kept: the streaming
     MFMA kernels of csrc/contrast.hip for float32 GPU tensors with d <= 256 outside the sizes where they measured slower, a
-    torch composition in row blocks of the queries otherwise, on GPU tensors with one TorchRouteWarning).  batched_loss calls the rebound method and is served as it stands.  Inputs that are not 2-D
+    torch composition in row blocks of the queries otherwise, on GPU tensors with one TorchRouteWarning).  Under torch.autocast
+    for the GPU, float32 and 16-bit inputs with d <= 256 are normalised in float32, cast once to the autocast dtype for that call
+    and run on the fp16 / bf16 MFMA kernels of csrc/contrast16.hip at the sizes where those measured no slower; the loss is
+    float32 and the gradients reach the inputs in their own dtype.  batched_loss calls the rebound method and is served as it stands.  Inputs that are not 2-D
     float tensors of one width reach the reference's method.
     netsmf=True rebinds NetSMF.forward in cogdl.models.emb.netsmf (opt-in: the draws are Philox's, not numpy's; num_round rounds
     become ceil(num_round / 2) passes over the CSR entries, so an odd num_round is rounded up; a node without edges gets a zero

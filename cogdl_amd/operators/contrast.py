@@ -22,7 +22,9 @@ kernels of csrc/contrast.hip -- score tiles of 64 x 64 from v_mfma_f32_32x32x2_f
 the scores recomputed in two backward passes (one per gradient), no float atomics, nothing of size block x N; it keeps q, k,
 skip, lse and one more [M] vector (what lse * tau does not hold of the row's normaliser in float32).  d above 256 is not
 chunked: route="hip" raises BackendError there and grace_loss takes the torch route with its warning.  split= overrides the
-number of slices the walked side is cut into (tests).
+number of slices the walked side is cut into (tests).  float16 and bfloat16 CUDA tensors run the same passes on
+v_mfma_f32_32x32x16_f16 / _bf16 (csrc/contrast16.hip): fp32 arithmetic on the operands as given, lse and its companion vector
+kept in float32, the returned lse and each gradient rounded once to the operands' dtype.
 
 The torch route (route=None or "torch" in pair_lse) is the torch composition -- matmul, the skipped entry masked to -inf, torch.logsumexp (the maximum subtracted: no
 precondition on the size of the scores) -- evaluated in row blocks of the queries, forward AND backward: the forward keeps q,
@@ -133,13 +135,25 @@ def slices(m, n, d, which):
     return int(_lib.hip().cogdl_hip_pair_lse_slices(int(m), int(n), int(d), ("fwd", "grad_q", "grad_k").index(which)))
 
 
+# the 16-bit operand types csrc/contrast16.hip serves, and their COGDL_HIP_* codes
+_HIP16 = {torch.float16: 1, torch.bfloat16: 2}
+# grace_loss(route=None) on 16-bit inputs: as _TORCH_FASTER, but measured on the 16-bit kernels against what those inputs ran
+# before (the blocked composition in their own dtype), and for d > 128 only.  Forward + backward, kernels / torch, float16 and
+# bfloat16: d <= 128 faster at every measured size (0.76x to 0.80x from 70 x 140 to 2708 x 5416, 0.48x at 8192 x 16384);
+# d = 256 0.88x / 0.91x at 1024 x 2048 = 2^21, SLOWER at 2708 x 5416 (1.24x / 1.19x: too few workgroups, as for float32),
+# 0.95x / 0.92x at 8192 x 16384 = 2^27, 0.84x / 0.82x and 0.59x / 0.57x beyond (profiles/contrast_bench.txt)
+_TORCH_FASTER16 = (1 << 21, 1 << 27)
+_TORCH_FASTER16_ABOVE_D = 128
+
+
 def _hip_served(q):
-    return q.is_cuda and q.dtype == torch.float32 and q.shape[1] <= HIP_MAX_D
+    return q.is_cuda and (q.dtype == torch.float32 or q.dtype in _HIP16) and q.shape[1] <= HIP_MAX_D
 
 
 class _HipLse(torch.autograd.Function):
-    """The kernels of csrc/contrast.hip.  Keeps q, k, skip, lse and corr ([M]: what lse * tau does not hold of a row's
-    normaliser in float32), and nothing else."""
+    """The kernels of csrc/contrast.hip (float32 q, k) and csrc/contrast16.hip (float16, bfloat16).  Keeps q, k, skip, lse and
+    corr ([M]: what lse * tau does not hold of a row's normaliser in float32), and nothing else.  lse and corr are float32 for
+    every operand dtype; the gradients arrive in the operands' dtype."""
 
     @staticmethod
     def forward(ctx, q, k, skip, tau, split):
@@ -149,8 +163,13 @@ class _HipLse(torch.autograd.Function):
         n_slices = slices(m, n, d, "fwd") if split is None else split
         ws, ws_bytes = _lib.workspace("cogdl_hip_pair_lse_workspace_bytes", dev, m, n, 2, n_slices)
         with _lib.on_device(dev):
-            rc = _lib.hip().cogdl_hip_pair_lse_fwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(skip), m, n, d, tau, n_slices, _lib.ptr(lse),
-                                                   _lib.ptr(corr), _lib.ptr(ws), ws_bytes, _lib.stream_of(q))
+            if q.dtype in _HIP16:
+                rc = _lib.hip().cogdl_hip_pair_lse16_fwd(_lib.ptr(q), _lib.ptr(k), _HIP16[q.dtype], _lib.ptr(skip), m, n, d, tau,
+                                                         n_slices, _lib.ptr(lse), _lib.ptr(corr), _lib.ptr(ws), ws_bytes,
+                                                         _lib.stream_of(q))
+            else:
+                rc = _lib.hip().cogdl_hip_pair_lse_fwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(skip), m, n, d, tau, n_slices,
+                                                       _lib.ptr(lse), _lib.ptr(corr), _lib.ptr(ws), ws_bytes, _lib.stream_of(q))
         _lib.check(rc, "pair_lse_fwd")
         ctx.tau, ctx.split = tau, split
         ctx.save_for_backward(q, k, skip, lse, corr)
@@ -173,21 +192,30 @@ class _HipLse(torch.autograd.Function):
         s_k = (slices(m, n, d, "grad_k") if ctx.split is None else ctx.split) if want_k else 1
         # one workspace, the larger of the two passes' (they run one after the other)
         rows, other, n_slices = max([(m, n, s_q), (n, m, s_k)], key=lambda a: a[0] * a[2] * (a[2] > 1))
-        ws, ws_bytes = _lib.workspace("cogdl_hip_pair_lse_workspace_bytes", dev, rows, other, d, n_slices)
+        half = q.dtype in _HIP16
+        ws, ws_bytes = _lib.workspace("cogdl_hip_pair_lse16_workspace_bytes" if half else "cogdl_hip_pair_lse_workspace_bytes", dev,
+                                      rows, other, d, n_slices)
         with _lib.on_device(dev):
-            rc = _lib.hip().cogdl_hip_pair_lse_grad(_lib.ptr(q), _lib.ptr(k), _lib.ptr(skip), _lib.ptr(lse), _lib.ptr(corr),
-                                                    _lib.ptr(grad), m, n, d, ctx.tau, s_q, s_k, _lib.ptr(g_q), _lib.ptr(g_k),
-                                                    _lib.ptr(ws), ws_bytes, _lib.stream_of(q))
+            if half:
+                rc = _lib.hip().cogdl_hip_pair_lse16_grad(_lib.ptr(q), _lib.ptr(k), _HIP16[q.dtype], _lib.ptr(skip), _lib.ptr(lse),
+                                                          _lib.ptr(corr), _lib.ptr(grad), m, n, d, ctx.tau, s_q, s_k, _lib.ptr(g_q),
+                                                          _lib.ptr(g_k), _lib.ptr(ws), ws_bytes, _lib.stream_of(q))
+            else:
+                rc = _lib.hip().cogdl_hip_pair_lse_grad(_lib.ptr(q), _lib.ptr(k), _lib.ptr(skip), _lib.ptr(lse), _lib.ptr(corr),
+                                                        _lib.ptr(grad), m, n, d, ctx.tau, s_q, s_k, _lib.ptr(g_q), _lib.ptr(g_k),
+                                                        _lib.ptr(ws), ws_bytes, _lib.stream_of(q))
         _lib.check(rc, "pair_lse_grad")
         return g_q, g_k, None, None, None
 
 
-def pair_lse(q, k, tau, skip=None, *, block=None, route=None, split=None, _skip_checked=False):
+def pair_lse(q, k, tau, skip=None, *, block=None, route=None, split=None, _skip_checked=False, _lse32=False):
     """q [M, d], k [N, d] -> lse [M] in the dtype of q.  route: None or "torch" -- the blocked composition (block: its query rows
-    per step), "hip" -- the kernels of csrc/contrast.hip (split: their slice count, for tests; by default the library's rule).
+    per step), "hip" -- the kernels of csrc/contrast.hip (float32) or csrc/contrast16.hip (float16, bfloat16: fp32 arithmetic on
+    the operands as given, lse the kernel's float32 value rounded once, the gradients rounded once in the operands' dtype);
+    split: their slice count, for tests; by default the library's rule.
     BackendError for arguments that are not 2-D floating tensors of one width and dtype, a tau that is not positive, a skip of
-    another shape, dtype or range, an unknown route, and for route="hip" on what the kernels do not serve: CPU tensors, a dtype
-    other than float32, d above 256."""
+    another shape, dtype or range, an unknown route, and for route="hip" on what the kernels do not serve: CPU tensors, float64,
+    d above 256."""
     if route not in ROUTES:
         raise _lib.BackendError("pair_lse: route must be one of %s (got %r)" % (ROUTES, route))
     if not (torch.is_tensor(q) and torch.is_tensor(k)) or q.dim() != 2 or k.dim() != 2 or q.shape[1] != k.shape[1]:
@@ -211,7 +239,7 @@ def pair_lse(q, k, tau, skip=None, *, block=None, route=None, split=None, _skip_
         raise _lib.BackendError("pair_lse: tensors on %s" % sorted({str(t.device) for t in tensors}))
     if route == "hip":
         if not _hip_served(q):
-            raise _lib.BackendError("pair_lse: route=\"hip\" serves float32 CUDA tensors with d <= %d (got %s on %s, d = %d); "
+            raise _lib.BackendError("pair_lse: route=\"hip\" serves float32, float16 and bfloat16 CUDA tensors with d <= %d (got %s on %s, d = %d); "
                                     "there is no fallback behind it" % (HIP_MAX_D, q.dtype, q.device, d))
         if split is not None and int(split) < 1:
             raise _lib.BackendError("pair_lse: split must be at least 1 (got %r)" % (split,))
@@ -221,22 +249,50 @@ def pair_lse(q, k, tau, skip=None, *, block=None, route=None, split=None, _skip_
         return q.new_empty((0,))
     if route == "hip":
         skip32 = None if skip is None else skip.to(torch.int32).contiguous()
-        return _HipLse.apply(q.contiguous(), k.contiguous(), skip32, tau, None if split is None else int(split))[0]
+        lse = _HipLse.apply(q.contiguous(), k.contiguous(), skip32, tau, None if split is None else int(split))[0]
+        return lse if _lse32 else lse.to(q.dtype)  # (16-bit operands: the kernel's float32 value, rounded once)
     if q.is_cuda:
         _note_torch_route("the blocked composition; route=\"hip\" runs the kernels of csrc/contrast.hip")
     return _BlockedLse.apply(q, k, skip, tau, _block_rows(q, k, block))
 
 
-def grace_loss(z1, z2, tau, *, block=None, route=None):
+def _grace_loss16(z1, z2, tau, dtype):
+    """grace_loss on the 16-bit kernels: the rows normalised in float32 and rounded once to `dtype`, the kernel's float32 lse
+    (not its rounded copy), <a_i, a_i> of the rounded rows in float32; a float32 scalar.  The gradient reaches z1, z2 in their own
+    dtype through the casts."""
+    a = torch.nn.functional.normalize(z1.float(), p=2, dim=-1).to(dtype)
+    b = torch.nn.functional.normalize(z2.float(), p=2, dim=-1).to(dtype)
+    skip = torch.arange(a.shape[0], device=a.device)
+    lse = pair_lse(a, torch.cat([a, b]), tau, skip=skip, route="hip", _skip_checked=True, _lse32=True)
+    a32 = a.float()
+    return torch.mean(lse - (a32 * a32).sum(1) / float(tau))
+
+
+def grace_loss(z1, z2, tau, *, block=None, route=None, cast=None):
     """The reference's GRACEModelWrapper.contrastive_loss(z1, z2) with self.tau = tau: z1 [M, d], z2 [N, d] -> scalar.
-    route=None: the kernels for what they serve (float32 CUDA tensors, d <= 256) except where they measured slower
-    (_TORCH_FASTER: between 2^21 and 2^27 scores), the torch route for everything else; "torch" / "hip" as for pair_lse."""
+    route=None: the kernels for what they serve (float32, float16 and bfloat16 CUDA tensors, d <= 256) except where they measured
+    slower (_TORCH_FASTER: between 2^21 and 2^27 scores; _TORCH_FASTER16 for 16-bit operands with d > 128), the torch route for everything
+    else; "torch" / "hip" as for pair_lse.  On the 16-bit kernels the rows are normalised in float32 and rounded once, and the loss
+    is a float32 scalar.  cast: torch.float16 or torch.bfloat16 -- what contrast_compat passes under torch.autocast: float32 or
+    16-bit CUDA inputs run the 16-bit kernels in that dtype wherever route=None picks them for such operands, and are treated as
+    without `cast` elsewhere."""
     if route not in ROUTES:
         raise _lib.BackendError("grace_loss: route must be one of %s (got %r)" % (ROUTES, route))
+    if cast is not None and cast not in _HIP16:
+        raise _lib.BackendError("grace_loss: cast must be torch.float16 or torch.bfloat16 (got %r)" % (cast,))
+    if route != "torch" and torch.is_tensor(z1) and torch.is_tensor(z2) and z1.dim() == 2 and z2.dim() == 2:
+        as16 = cast if cast is not None and z1.dtype == torch.float32 else z1.dtype
+        scores = z1.shape[0] * (z1.shape[0] + z2.shape[0])
+        if (as16 in _HIP16 and z1.is_cuda and z2.device == z1.device and z2.dtype == z1.dtype and z1.shape[0] >= 1
+                and z2.shape[1] == z1.shape[1] and 1 <= z1.shape[1] <= HIP_MAX_D and max(z1.shape[0], z2.shape[0]) < 2 ** 30
+                and (route == "hip" or z1.shape[1] <= _TORCH_FASTER16_ABOVE_D
+                     or not _TORCH_FASTER16[0] < scores < _TORCH_FASTER16[1])):
+            return _grace_loss16(z1, z2, tau, as16)
     a = torch.nn.functional.normalize(z1, p=2, dim=-1)
     b = torch.nn.functional.normalize(z2, p=2, dim=-1)
     if route is None:
-        served = a.dim() == 2 and b.dim() == 2 and a.shape[0] >= 1 and b.is_cuda and b.dtype == a.dtype and _hip_served(a)
+        served = (a.dim() == 2 and b.dim() == 2 and a.shape[0] >= 1 and b.is_cuda and b.dtype == a.dtype
+                  and a.dtype == torch.float32 and _hip_served(a))
         scores = a.shape[0] * (a.shape[0] + b.shape[0]) if served else 0
         route = "hip" if served and not _TORCH_FASTER[0] < scores < _TORCH_FASTER[1] else "torch"
     skip = torch.arange(a.shape[0], device=a.device)  # (in range by construction: M <= M + N keys)

@@ -1562,6 +1562,25 @@ COGDL_API int cogdl_hip_pair_lse_grad(const float *q, const float *k, const int3
                        const float *g, int64_t M, int64_t N, int64_t d, float tau, int64_t slices_q, int64_t slices_k,
                        float *grad_q, float *grad_k, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The same three passes on 16-bit operands (added within ABI v9: new symbols only; csrc/contrast16.hip, v_mfma_f32_32x32x16_f16 /
+ * _bf16): dtype = COGDL_HIP_F16 | COGDL_HIP_BF16 (anything else: COGDL_HIP_EUNSUPPORTED) is the element type of q, k, grad_q and
+ * grad_k; lse, corr and g stay fp32.  fp32 arithmetic on the operands as given (their products are exact in fp32), one rounding
+ * to nearest even where a gradient is stored: in the kernel's store with one slice, in the fold of the fp32 partials with several.
+ * The backward's second operand W is rounded once to the operand type, held scaled by a power of two so that a row's largest
+ * entries are normal numbers of fp16 whatever N and g are (grad_k: one exponent per launch, found on the device from g and lse).
+ * Slices: cogdl_hip_pair_lse_slices.  Workspace of the forward: cogdl_hip_pair_lse_workspace_bytes(M, N, 2, slices), as above;
+ * of the backward: cogdl_hip_pair_lse16_workspace_bytes(M, N, d, slices) = that function's value plus 256 bytes that the
+ * backward needs with one slice too (grad_k: ask with (N, M, d, slices_k)); both passes use the one workspace.  Pointers to
+ * 16-bit data aligned to 2 bytes; 16-byte loads are used where d % 8 == 0 and q and k are 16-byte aligned.  Everything else as
+ * for the fp32 entries. */
+COGDL_API size_t cogdl_hip_pair_lse16_workspace_bytes(int64_t M, int64_t N, int64_t d, int64_t slices);
+COGDL_API int cogdl_hip_pair_lse16_fwd(const void *q, const void *k, int dtype, const int32_t *skip, int64_t M, int64_t N,
+                       int64_t d, float tau, int64_t slices, float *lse, float *corr, void *workspace, size_t workspace_bytes,
+                       void *stream);
+COGDL_API int cogdl_hip_pair_lse16_grad(const void *q, const void *k, int dtype, const int32_t *skip, const float *lse,
+                       const float *corr, const float *g, int64_t M, int64_t N, int64_t d, float tau, int64_t slices_q,
+                       int64_t slices_k, void *grad_q, void *grad_k, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------------------------------------------------
  * Inner-product decoder loss (added within ABI v9: new symbols only; csrc/recon.hip).  z fp32 [N, d]; E weighted edges
  * (row[e], col[e], w[e]), int32 endpoints in [0, N) -- the caller's to guarantee, they are not checked on the device --
